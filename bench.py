@@ -17,7 +17,12 @@ renders its tiles at SPP_PER_STEP*N samples per step (fixed per-GPU work: weak s
 torch.distributed (gloo, host memory) is the harness's control plane only: it hands RCCL's
 unique id from rank 0 to the others, and carries the barriers and the max-over-ranks time.
 
-At N=1 the line also carries `configs`: C2 (marched SDF scene, 256 march steps) and C3 (10k
+A plain run does only that: set up, warm up, time the K steps, write the outputs if
+--dump-outputs is given, print the line.  Everything else below runs under --full alone: the
+untimed reruns behind `roofline` and `work`, the oracle window of every timed frame, the CPU
+baselines and the `configs` block.
+
+With --full at N=1 the line also carries `configs`: C2 (marched SDF scene, 256 march steps) and C3 (10k
 spheres, BVH) at full spp with their own roofline and CPU baseline, C4's 3840x2160 frame at
 256 spp (the N=1 leg of the 8-GPU config), and C0 (the reference's CPU case, 400x225x64 at
 depth 8) timed on the GPU and on the host cores.
@@ -230,6 +235,46 @@ def check_gathered(shard_u8, n_mine, frame_u8, W, H, n, rank, spp_total):
             "gathered frame differs from rank 0's shard"
 
 
+DUMP_PIXELS = 1 << 19      # --dump-outputs: at most this many pixels of the frame (88 B each as written: 46 MB)
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, frame_u8, W, H):
+    """--dump-outputs: the gathered frame of the timed region's last step (what om_gather_frame hands
+    rank 0: W*H Stats after all K steps), one <field>.npy per Stats field.  A frame of more than
+    DUMP_PIXELS pixels is written as a fixed sample of that many (RandomState(DUMP_SEED)'s
+    permutation of the pixel ids, sorted; `pixel.npy` names them), every field exact: f32 stays f32,
+    integers go to float64, the 64-bit bloom word as its (low, high) 32-bit halves.  Every value
+    written is finite: where `sum` or `avg_depth` is infinite (a sky pixel's avg_depth) or NaN the
+    array holds 0 and `<field>_class.npy` says which (0 finite, 1 +inf, 2 -inf, 3 NaN)."""
+    fr = frame_u8.view(L.PIXEL_STATS_DTYPE)
+    assert fr.size == W * H
+    if fr.size > DUMP_PIXELS:
+        pixel = np.sort(np.random.RandomState(DUMP_SEED).permutation(fr.size)[:DUMP_PIXELS])
+    else:
+        pixel = np.arange(fr.size)
+    fr = fr[pixel]
+    def finite(a):
+        """(a with 0 where it is not finite, the class of each value: 0 finite, 1 +inf, 2 -inf, 3 NaN)."""
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        cls = np.where(np.isnan(a), 3, np.where(np.isposinf(a), 1, np.where(np.isneginf(a), 2, 0))).astype(np.float32)
+        return np.where(cls == 0, a, np.float32(0)), cls
+
+    (fsum, sum_class), (depth, depth_class) = finite(fr["sum"]), finite(fr["avg_depth"])
+    arrays = {"pixel": pixel.astype(np.float64),
+              "sum": fsum, "sum_class": sum_class,
+              "n": fr["n"].astype(np.float64),
+              "avg_depth": depth, "avg_depth_class": depth_class,     # a sky pixel's avg_depth is +inf
+              "bad_avgs": fr["bad_avgs"].astype(np.float64),
+              "color": fr["color"].astype(np.float32),
+              "flags": fr["flags"].astype(np.float32),
+              "bloom": np.stack([fr["bloom"] & np.uint64(0xFFFFFFFF), fr["bloom"] >> np.uint64(32)], axis=1).astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 1000 * 1000
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a, allow_pickle=False)
+
+
 def timed_region(ctl, steps, step, gather, sync):
     """K steps plus the gather, bracketed by a barrier + device synchronisation on both sides;
     -> the max over ranks of the wall time."""
@@ -299,8 +344,10 @@ def run_host_rehearsal(name, ctl, steps, warmup, spp_per_step):
             "window_parity": None, "nranks_seen": nranks_seen, "work": None, "shard_capacity": cap, "shard_pixels": n_mine}
 
 
-def run_config(name, args, ctl, local_rank, steps, warmup, spp_per_step, timing_mode, pmc_ok=True):
-    """One config through the product path; returns the measured fields (value, roofline, work)."""
+def run_config(name, args, ctl, local_rank, steps, warmup, spp_per_step, timing_mode, pmc_ok=True, keep_frame=False):
+    """One config through the product path; returns the measured fields (value; under --full also
+    the roofline, work and window parity, which take untimed runs of their own).  keep_frame: the
+    gathered frame of the timed region's last step rides along as `frame` (rank 0; --dump-outputs)."""
     if args.host_rehearsal:
         return run_host_rehearsal(name, ctl, steps, warmup, spp_per_step)
     cfg = CONFIGS[name]
@@ -329,7 +376,7 @@ def run_config(name, args, ctl, local_rank, steps, warmup, spp_per_step, timing_
     def step():
         comm.render_shard(cam, p, sh.data_ptr(), sptr)
 
-    for count in (1, 0):                                      # warm the counting and the production build
+    for count in ((1, 0) if args.full else (0,)):             # warm the production build (--full: the counting one too)
         L.check(L.lib.om_set_counting(ctx, count), ctx)
         for _ in range(warmup):
             step()
@@ -362,6 +409,14 @@ def run_config(name, args, ctl, local_rank, steps, warmup, spp_per_step, timing_
     host = sh.cpu().numpy().copy()
     frame_u8 = frame.cpu().numpy()
     check_gathered(host, n_mine, frame_u8, W, H, n, rank, spp_total)
+    value = W * H * spp_total / elapsed / 1e6        # all ranks together (each renders its 1/N of the pixels)
+    kept = frame_u8 if keep_frame and rank == 0 else None
+    if not args.full:                                # a plain run ends here: the headline figure alone
+        comm.close()
+        frozen.close()
+        return {"value": round(value, 3), "elapsed_s": elapsed, "steps": steps, "W": W, "H": H, "depth": depth,
+                "spp_total": spp_total, "spp_step": spp_step, "mega": None, "roofline": None, "window_parity": None,
+                "nranks_seen": nranks_seen, "work": None, "frame": kept}
     parity = None
     if rank == 0 and not args.no_window_parity:
         parity = window_parity(name, frame_u8, W, H, spp_total, depth, cfg["march_steps"])
@@ -397,8 +452,6 @@ def run_config(name, args, ctl, local_rank, steps, warmup, spp_per_step, timing_
     comm.close()
     frozen.close()
 
-    total_samples = W * H * spp_total        # all ranks together (each renders its 1/N of the pixels)
-    value = total_samples / elapsed / 1e6
     marched = cfg["scene"] == "S-marched"
 
     # roofline of the dominant kernel: the trace+shade bounce family (all its launches: bounce 0,
@@ -452,7 +505,7 @@ def run_config(name, args, ctl, local_rank, steps, warmup, spp_per_step, timing_
     return {
         "value": round(value, 3), "elapsed_s": elapsed, "steps": steps, "W": W, "H": H, "depth": depth,
         "spp_total": spp_total, "spp_step": spp_step, "mega": mega, "roofline": roof,
-        "window_parity": parity, "nranks_seen": nranks_seen,
+        "window_parity": parity, "nranks_seen": nranks_seen, "frame": kept,
         "work": {"segments_per_sample": round(ctr.segments / max(1, ctr.samples), 4),
                  "prim_tests_per_segment": round(ctr.prim_tests / max(1, ctr.segments), 3),
                  "box_tests_per_segment": round(ctr.pre_tests / max(1, ctr.segments), 3),
@@ -500,15 +553,21 @@ def main():
                          "launch = around every launch (per-kernel breakdown); off = none and no roofline")
     ap.add_argument("--primary-lists", default="auto", choices=["off", "auto", "on"],
                     help="bounce-0 per-tile candidate lists (DESIGN.md §5.10); auto = when they average <= 12")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the untimed reruns behind `roofline` and `work`, the "
+                         "oracle window of every timed frame, the CPU baselines and the `configs` block "
+                         "(C1_frame/C2/C3/C4/C0/C1_adaptive at N=1); the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the timed path delivered (rank 0) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="quick mode: the headline config only (no CPU baselines, no `configs` block)")
-    ap.add_argument("--no-extras", action="store_true", help="no `configs` block (C2/C3/C0) at N=1")
+                    help="--full, quick mode: the headline config only (no CPU baselines, no `configs` block)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: no `configs` block (C2/C3/C0) at N=1")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--host-rehearsal", action="store_true",
                     help="tests only: run the N>1 control flow on CPU processes (gloo), RCCL replaced by HostComm; "
                          "renders nothing, prints no measurement")
     ap.add_argument("--no-window-parity", action="store_true",
-                    help="skip the oracle window of each timed frame (untimed; a few seconds of host CPU)")
+                    help="--full: skip the oracle window of each timed frame (untimed; a few seconds of host CPU)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
 
@@ -527,7 +586,8 @@ def main():
     steps = args.steps
     if steps is None:
         steps = cfg["spp"] // args.spp_per_step if args.config != "C4" else cfg["spp"] // args.spp_per_step
-    r = run_config(args.config, args, ctl, local_rank, steps, args.warmup, args.spp_per_step, args.kernel_timing)
+    r = run_config(args.config, args, ctl, local_rank, steps, args.warmup, args.spp_per_step, args.kernel_timing,
+                   keep_frame=bool(args.dump_outputs))
     if args.host_rehearsal:                  # no device ran: a rehearsal record, never a metric line
         if rank == 0:
             print(json.dumps({"host_rehearsal": True, "config": args.config, "n_ranks": world_size, "steps": steps,
@@ -536,8 +596,11 @@ def main():
         ctl.close()
         return
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r.pop("frame"), r["W"], r["H"])
+
     extras = None
-    quick = args.no_cpu_baseline or args.no_extras
+    quick = not args.full or args.no_cpu_baseline or args.no_extras
     if rank == 0 and world_size == 1 and not quick and args.config == "C1":
         extras = {}
         # C1_frame: exactly the quoted "1080p@512spp" frame, one fresh frame of 4 x 128-spp calls
@@ -559,7 +622,7 @@ def main():
         extras["C0"] = run_c0(args)
         extras["C1_adaptive"] = run_adaptive(args)
     cpu = None
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world_size == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.config, args.cpu_budget)
         cpu["second"] = cpu_baseline(args.config, args.cpu_budget, "liboro_v3.so")
         cpu["all_cores"] = cpu_baseline(args.config, args.cpu_budget, threads=-1)   # nproc-1 and nproc
@@ -584,10 +647,13 @@ def main():
                        "parallelism": f"tile{world_size}", "gather": "RCCL send/recv (om_gather_frame)",
                        "rccl_library": rccl[0], "rccl_version": rccl[1],
                        "kernel": args.kernel,
+                       # what `auto` resolved to shows in the per-launch rerun (--full)
                        "pipeline": args.pipeline + (("->megakernel" if r["mega"] else "->wavefront")
-                                                    if args.pipeline == "auto" else ""),
+                                                    if args.pipeline == "auto" and r["mega"] is not None else ""),
                        "tail_bounce": args.tail or "default", "streams": args.streams},
             "nranks_seen": r["nranks_seen"],
+            "full": args.full,                       # the fields below are measured under --full only (else null)
+            "outputs": args.dump_outputs,
             "window_parity": r["window_parity"],
             "hbm_gbs": r["roofline"]["hbm_achieved_gbs"] if r["roofline"] else None,
             "roofline": r["roofline"],

@@ -30,6 +30,52 @@ def test_pmc_fields_from_committed_summaries(bench, cfg):
     assert bench.pmc_fields("C9") is None
 
 
+@pytest.mark.parametrize("W,H", [(64, 48), (1024, 520)])       # a whole frame; one larger than the sample
+def test_dump_outputs_fields_exact_and_repeatable(bench, tmp_path, W, H):
+    """--dump-outputs: every Stats field of the frame (or of the fixed pixel sample of a frame
+    larger than DUMP_PIXELS) comes back exactly from float32/float64 .npy files, the same pixels
+    on every call, within the 64 MB the option allows; every value written is finite, the infinities
+    (a sky pixel's avg_depth) and NaNs of the f32 fields carried by <field>_class.npy."""
+    import numpy as np
+    from raytracingoneweekend_amd import _lib as L
+    rng = np.random.RandomState(3)
+    fr = np.zeros(W * H, dtype=L.PIXEL_STATS_DTYPE)
+    fr["bloom"] = rng.randint(0, 1 << 32, W * H).astype(np.uint64) << np.uint64(31) | np.uint64(1)
+    fr["sum"] = rng.rand(W * H, 3).astype(np.float32) * 512
+    fr["n"] = rng.randint(0, 1 << 31, W * H)
+    fr["avg_depth"] = rng.rand(W * H).astype(np.float32) * 50
+    fr["avg_depth"][::3] = np.inf
+    fr["avg_depth"][5::7] = np.nan
+    fr["sum"][1::5, 1] = -np.inf
+    fr["sum"][2::11] = (np.nan, np.inf, 1.0)
+    fr["bad_avgs"] = rng.randint(0, 6, W * H)
+    fr["color"] = rng.randint(0, 256, (W * H, 3))
+    fr["flags"] = rng.randint(0, 256, W * H)
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    bench.dump_outputs(a, fr.view(np.uint8).reshape(-1), W, H)
+    bench.dump_outputs(b, fr.view(np.uint8).reshape(-1).copy(), W, H)
+    names = sorted(os.listdir(a))
+    assert names == sorted(f + ".npy" for f in ("pixel", "sum", "sum_class", "n", "avg_depth", "avg_depth_class",
+                                                  "bad_avgs", "color", "flags", "bloom"))
+    got = {f[:-4]: np.load(os.path.join(a, f), allow_pickle=False) for f in names}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 * 1000 * 1000
+    for f in names:
+        assert np.array_equal(got[f[:-4]], np.load(os.path.join(b, f), allow_pickle=False))
+    pixel = got["pixel"].astype(np.int64)
+    assert pixel.size == min(W * H, bench.DUMP_PIXELS) and np.all(np.diff(pixel) > 0) and pixel[-1] < W * H
+    exp = fr[pixel]
+    for f in ("n", "bad_avgs", "color", "flags"):
+        assert np.array_equal(got[f], exp[f]), f
+    for f in ("sum", "avg_depth"):
+        cls = got[f + "_class"]
+        assert (cls == 1).any() and (cls == 3).any() and (got[f][cls != 0] == 0).all()
+        back = np.select([cls == 1, cls == 2, cls == 3], [np.inf, -np.inf, np.nan], got[f]).astype(np.float32)
+        assert np.array_equal(back, exp[f], equal_nan=True), f
+    bloom = got["bloom"].astype(np.uint64)
+    assert np.array_equal(bloom[:, 0] | bloom[:, 1] << np.uint64(32), exp["bloom"])
+
+
 def _free_port():
     import socket
     s = socket.socket()

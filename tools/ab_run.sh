@@ -21,7 +21,7 @@ for c in $CFGS; do
   : > "$OUT/ab_$c.jsonl"
   for v in $VARS; do
     echo "{\"variant\": \"$v\"}" >> "$OUT/ab_$c.jsonl"
-    OM_LIB=$PWD/_abl/lib_$v.so timeout -k 10 200 python bench.py --warmup 2 --no-cpu-baseline --no-window-parity --config $c "$@" \
+    OM_LIB=$PWD/_abl/lib_$v.so timeout -k 10 200 python bench.py --full --warmup 2 --no-cpu-baseline --no-window-parity --config $c "$@" \
         >> "$OUT/ab_$c.jsonl" 2>> "$OUT/ab.err" || { echo "variant $v $c failed"; exit 1; }
   done
 done

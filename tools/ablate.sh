@@ -118,7 +118,7 @@ mkdir -p "$OUT"
 : > "$OUT/abl.jsonl"
 for k in ${VARIANTS:-base fastdiv contract ftz}; do
   echo "{\"variant\": \"$k\"}" >> "$OUT/abl.jsonl"
-  OM_LIB=$PWD/_abl/lib_$k.so timeout -k 10 200 python bench.py --steps ${STEPS:-8} --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} "${@:3}" \
+  OM_LIB=$PWD/_abl/lib_$k.so timeout -k 10 200 python bench.py --full --steps ${STEPS:-8} --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} "${@:3}" \
       >> "$OUT/abl.jsonl" 2>> "$OUT/abl.err" || { echo "variant $k failed"; exit 1; }
 done
 echo ok

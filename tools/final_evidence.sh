@@ -10,7 +10,8 @@ P=gpurun_out/r06_final6_pmc
 for c in C1 C2 C3 C4 C1_adaptive; do cp $P/pmc_summary_$c.json profiles/; done
 cp $P/pmc_traffic_C1.json profiles/pmc_traffic.json
 for c in C2 C3 C4 C1_adaptive; do cp $P/pmc_traffic_$c.json profiles/; done
-timeout -k 10 300 python bench.py > gpurun_out/r06_final6/bench_final.json 2> gpurun_out/r06_final6/bench_final.err || exit 1
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/r06_final6/driver1.json 2>/dev/null || exit 1
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/r06_final6/driver2.json 2>/dev/null || exit 1
+O=${P%_pmc}        # the folder of the first step's evidence
+timeout -k 10 300 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err || exit 1
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/driver1.json 2>/dev/null || exit 1
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/driver2.json 2>/dev/null || exit 1
 echo ok

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 TAG=${1:-pmc}; shift
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-ARGS="--steps 4 --warmup 1 --no-cpu-baseline --no-window-parity $*"
+ARGS="--full --steps 4 --warmup 1 --no-cpu-baseline --no-window-parity $*"
 # PMC_CMD: another program to profile (e.g. the adaptive frame, tools/adaptive_bench.py)
 CMD=${PMC_CMD:-"python bench.py $ARGS"}
 # the build the passes profile (om_build_id), for bench.py's pmc fields (pmc_summary.py reads it)

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 : > "$OUT/sweep.jsonl"
 for item in "$@"; do
   echo "{\"variant\": \"${item%%|*}\"}" >> "$OUT/sweep.jsonl"
-  timeout -k 10 200 python bench.py --warmup 2 --no-cpu-baseline --no-window-parity --no-extras ${item#*|} \
+  timeout -k 10 200 python bench.py --full --warmup 2 --no-cpu-baseline --no-window-parity --no-extras ${item#*|} \
       >> "$OUT/sweep.jsonl" 2>> "$OUT/sweep.err" || { echo "item $item failed"; exit 1; }
 done
 python tools/ab_print.py "$OUT/sweep.jsonl"
