@@ -342,7 +342,7 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
     // breadth-first so the top levels, which every ray visits, are the first nodes: a tree
     // too big for LDS stages that prefix there (om_wavefront.hip, OM_WF_HYB_BYTES).
     // direct leaf codes: when every record index fits 11 bits and every leaf holds
-    // at most 15 records (S-traced: 485 records, leaves <= 8), a leaf child's 16-bit code is
+    // at most 15 records (S-traced: 482 records, leaves <= 2; every regime: DESIGN.md §5.6), a leaf child's 16-bit code is
     // OM_LEAF | first << 4 | count, so the traversal needs no leaf-table read to enter a leaf;
     // the table is still emitted (same order) for the other consumers.
     // (both conditions checked here, not assumed from the builder's leaf cap: a count above 15

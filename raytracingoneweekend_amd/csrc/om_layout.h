@@ -177,9 +177,17 @@ struct OM_ALIGN16 OmBvh2NodeH {
     uint16_t c0, c1;
     uint32_t pad;
 };
-// f32 BVH2 nodes + leaf table of at most this many bytes are staged whole in LDS per workgroup;
-// a bigger tree is read through L2 (half nodes, an LDS prefix) and built with smaller leaves
+// f32 BVH2 nodes + leaf table of at most this many bytes (nodes counted at their 64 B in memory)
+// are staged whole in LDS per workgroup; a bigger tree is read through L2 (half nodes, an LDS
+// prefix) and built with smaller leaves.  The wavefront stages the nodes OM_B2_NODE_STRIDE (80) B
+// apart, so an admitted tree occupies nodes*80 + leaves*4 bytes there: at most 50 KiB at the
+// budget, 74 KiB with a 24-entry lane stack for 512 lanes (one workgroup may use all 160 KiB
+// of a gfx950 CU).  om::plan_trees (om_world.h) decides.
 constexpr uint32_t kB2LdsBudget = 40u * 1024u;
+// the same cut for the BVH4 (112-B nodes + the leaf table, staged unpadded)
+constexpr uint32_t kB4LdsBudget = 40u * 1024u;
+// the megakernel's staged SBVH (nodes + records) per 512-lane workgroup
+constexpr uint32_t kLdsBudget = 96u * 1024u;
 
 // Device view of a frozen world (passed by value as a kernel argument).
 struct OmSceneDev {
@@ -208,8 +216,9 @@ struct OmSceneDev {
     const uint32_t* b2leaves;
     const OmAlwaysRec* always2_rec;  // always2 with boxes (BVH2 traversal)
     uint32_t n_b2nodes, n_b2leaves;
-    uint32_t b2_lds_bytes;        // node bytes when they fit the LDS budget, else 0 (global nodes)
-    uint32_t b2_stack;            // lane-stack entries the tree needs (its internal depth, <= 24)
+    uint32_t b2_lds_bytes;        // nodes*64 + leaves*4 when within kB2LdsBudget, else 0 (global nodes); the megakernel
+                                  // stages exactly these bytes, the wavefront nodes*80 + leaves*4 (b2_stage_bytes)
+    uint32_t b2_stack;           // lane-stack entries the tree needs (its internal depth, <= 24)
     uint32_t b2_direct;           // leaf codes are OM_LEAF | first_record << 4 | count (om_bvh.cpp), not table indices
     // BVH4 collapsed from the BVH2 (same leaf table / records / always2)
     const OmBvh4Node* b4nodes;

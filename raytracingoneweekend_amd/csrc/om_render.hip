@@ -45,7 +45,6 @@ constexpr int kBlock = 256;
 enum { MODE_BRUTE = 1, MODE_CULLED = 2, MODE_BVH = 3, MODE_SBVH_LDS = 4, MODE_SBVH_GLOBAL = 5, MODE_BVH2 = 6 };
 constexpr int kStack2 = 24;                    // BVH2 lane-stack bound (om_upload_world checks the depth)
 constexpr int kBlockLds = 512;
-constexpr uint32_t kLdsBudget = 96u * 1024u;   // staged scene per workgroup (160 KiB per CU)
 
 }  // namespace
 
@@ -635,28 +634,15 @@ om_status om_upload_world(om_ctx* c, const om_world* w) {
     S.n_bvh_nodes = (uint32_t)fw.bvh.size();
     S.n_always = (uint32_t)fw.always.size();
     S.n_snodes = (uint32_t)fw.snodes.size(); S.n_srecs = (uint32_t)fw.srecs.size(); S.n_always2 = (uint32_t)fw.always2.size();
-    const size_t lds = fw.snodes.size() * sizeof(OmSkipNode) + fw.srecs.size() * sizeof(OmAffineTest);
-    S.lds_bytes = lds <= kLdsBudget ? (uint32_t)(lds < 16 ? 16 : lds) : 0u;
-    // compressed BVH2: usable when node and leaf ids fit the 15-bit codes and its depth fits
-    // the lane-stack bound (otherwise the wavefront path uses the global-memory BVH)
-    const bool b2_ok = !fw.b2nodes.empty() && fw.b2nodes.size() < 32768u && fw.b2leaves.size() < 32768u &&
-                       fw.b2_depth <= 24u;   // lane stack bound (om_wavefront.hip kStackDepth)
-    S.n_b2nodes = b2_ok ? (uint32_t)fw.b2nodes.size() : 0u;
-    S.n_b2leaves = b2_ok ? (uint32_t)fw.b2leaves.size() : 0u;
-    S.b2_direct = b2_ok ? fw.b2_direct : 0u;
-    S.b2_stack = b2_ok ? fw.b2_depth : 0u;   // one push per internal level on the current path, deepest included
-    const size_t b2_bytes = fw.b2nodes.size() * sizeof(OmBvh2Node) + fw.b2leaves.size() * 4u;
-    S.b2_lds_bytes = (b2_ok && b2_bytes <= kB2LdsBudget) ? (uint32_t)((b2_bytes + 15u) & ~(size_t)15u) : 0u;
-    // BVH4 (same leaf table): up to 3 pushes per level + 3 spare entries for the
-    // unconditional pushes, within the 48-entry bound of om_wavefront.hip
-    const uint32_t b4_stack = 3u * fw.b4_depth + 3u;
-    const bool b4_ok = b2_ok && !fw.b4nodes.empty() && fw.b4nodes.size() < 32768u && b4_stack <= 48u;
-    if (b4_ok && (s = upload(c, fw.b4nodes, &S.b4nodes)) != OM_OK) return s;
-    if (b4_ok && (s = upload(c, fw.b4h, &S.b4h)) != OM_OK) return s;
-    S.n_b4nodes = b4_ok ? (uint32_t)fw.b4nodes.size() : 0u;
-    S.b4_stack = b4_ok ? b4_stack : 0u;
-    const size_t b4_bytes = fw.b4nodes.size() * sizeof(OmBvh4Node) + fw.b2leaves.size() * 4u;
-    S.b4_lds_bytes = (b4_ok && b4_bytes <= 40u * 1024u) ? (uint32_t)((b4_bytes + 15u) & ~(size_t)15u) : 0u;
+    // which trees are usable and which are staged in LDS: om::plan_trees (om_world.h)
+    const om::TreePlan plan = om::plan_trees(fw);
+    S.lds_bytes = plan.lds_bytes;
+    S.n_b2nodes = plan.n_b2nodes; S.n_b2leaves = plan.n_b2leaves;
+    S.b2_direct = plan.b2_direct; S.b2_stack = plan.b2_stack; S.b2_lds_bytes = plan.b2_lds_bytes;
+    if (plan.b4_ok && (s = upload(c, fw.b4nodes, &S.b4nodes)) != OM_OK) return s;
+    if (plan.b4_ok && (s = upload(c, fw.b4h, &S.b4h)) != OM_OK) return s;
+    S.n_b4nodes = plan.b4_ok ? (uint32_t)fw.b4nodes.size() : 0u;
+    S.b4_stack = plan.b4_stack; S.b4_lds_bytes = plan.b4_lds_bytes;
     OM_HIP(c, hipStreamSynchronize(c->stream));
     c->have_world = true;
     return OM_OK;

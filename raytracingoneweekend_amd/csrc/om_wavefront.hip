@@ -67,6 +67,9 @@ constexpr int kStackDepth = 24;                                   // BVH2 per-la
 // f32 BVH2 nodes staged in LDS sit OM_B2_NODE_STRIDE bytes apart (om_tuning.h)
 constexpr uint32_t kB2Stride = OM_B2_NODE_STRIDE;
 static_assert(kB2Stride % 16u == 0u && kB2Stride >= sizeof(OmBvh2Node), "16-B aligned node slots");
+// stage_scene turns a child index into a slot offset in 16-B units (index * kB2Stride / 16): for
+// every tree the budget admits, the scaled code must still read as a node, not as a leaf
+static_assert(kB2LdsBudget / sizeof(OmBvh2Node) * (kB2Stride / 16u) < OM_LEAF, "scaled BVH2 child codes stay below OM_LEAF");
 // LDS bytes of the lane stack: S.b2_stack entries per lane (the tree's internal depth, 9 for
 // S-traced: 9 KiB per 512-lane workgroup instead of 24 KiB at the 24-entry bound).
 template <int TR>

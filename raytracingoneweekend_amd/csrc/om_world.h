@@ -58,6 +58,43 @@ struct FrozenWorld {
     uint32_t offsets[K_N + 1];         // global index offset per kind, offsets[K_N] = total
 };
 
+// Which traversal regime a frozen world gets (om_upload_world copies these into OmSceneDev; the
+// host-only tests/cpp/tree_regimes.cpp reports them).  A zero *_lds_bytes means "not staged":
+// the tree is read through L2 (BVH2 / BVH4) or from global memory (the megakernel's SBVH).
+struct TreePlan {
+    bool b2_ok = false;            // compressed BVH2 usable: 15-bit node / leaf codes, depth <= 24
+    uint32_t n_b2nodes = 0, n_b2leaves = 0, b2_direct = 0;
+    uint32_t b2_stack = 0;         // lane-stack entries: one push per internal level, deepest included
+    uint32_t b2_lds_bytes = 0;     // nodes (64 B each) + leaf table, rounded to 16, when within kB2LdsBudget
+    bool b4_ok = false;
+    uint32_t b4_stack = 0;         // 3 pushes per level + 3 spare entries for the unconditional pushes
+    uint32_t b4_lds_bytes = 0;     // nodes (112 B each) + leaf table, rounded to 16, when within kB4LdsBudget
+    uint32_t lds_bytes = 0;        // SBVH nodes + records when within kLdsBudget (at least 16)
+};
+
+inline TreePlan plan_trees(const FrozenWorld& fw) {
+    TreePlan p;
+    const size_t lds = fw.snodes.size() * sizeof(OmSkipNode) + fw.srecs.size() * sizeof(OmAffineTest);
+    p.lds_bytes = lds <= kLdsBudget ? (uint32_t)(lds < 16 ? 16 : lds) : 0u;
+    // compressed BVH2: usable when node and leaf ids fit the 15-bit codes and its depth fits
+    // the lane-stack bound (otherwise the wavefront path uses the global-memory BVH)
+    p.b2_ok = !fw.b2nodes.empty() && fw.b2nodes.size() < 32768u && fw.b2leaves.size() < 32768u &&
+              fw.b2_depth <= 24u;   // lane stack bound (om_wavefront.hip kStackDepth)
+    p.n_b2nodes = p.b2_ok ? (uint32_t)fw.b2nodes.size() : 0u;
+    p.n_b2leaves = p.b2_ok ? (uint32_t)fw.b2leaves.size() : 0u;
+    p.b2_direct = p.b2_ok ? fw.b2_direct : 0u;
+    p.b2_stack = p.b2_ok ? fw.b2_depth : 0u;
+    const size_t b2_bytes = fw.b2nodes.size() * sizeof(OmBvh2Node) + fw.b2leaves.size() * 4u;
+    p.b2_lds_bytes = (p.b2_ok && b2_bytes <= kB2LdsBudget) ? (uint32_t)((b2_bytes + 15u) & ~(size_t)15u) : 0u;
+    // BVH4 (same leaf table): within the 48-entry bound of om_wavefront.hip
+    const uint32_t b4_stack = 3u * fw.b4_depth + 3u;
+    p.b4_ok = p.b2_ok && !fw.b4nodes.empty() && fw.b4nodes.size() < 32768u && b4_stack <= 48u;
+    p.b4_stack = p.b4_ok ? b4_stack : 0u;
+    const size_t b4_bytes = fw.b4nodes.size() * sizeof(OmBvh4Node) + fw.b2leaves.size() * 4u;
+    p.b4_lds_bytes = (p.b4_ok && b4_bytes <= kB4LdsBudget) ? (uint32_t)((b4_bytes + 15u) & ~(size_t)15u) : 0u;
+    return p;
+}
+
 uint64_t bloom_hash(uint64_t id);      // utils.rs:94-107
 
 }  // namespace om

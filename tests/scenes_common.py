@@ -78,6 +78,11 @@ def compare_stats_nan_payload(got, exp, label=""):
     return nb, msg
 
 
+TIE_PALETTE = [("lambertian", (0.8, 0.3, 0.2), 0.0, 0.0), ("metal", (0.7, 0.8, 0.9), 0.1, 0.0),
+               ("dielectric", (0.0, 0.0, 0.0), 0.0, 1.5), ("lambertian", (0.1, 0.6, 0.2), 0.0, 0.0),
+               ("metal", (0.9, 0.6, 0.3), 0.4, 0.0)]            # tie_scene's
+
+
 def tie_scene(om, O, duplicates=True):
     """Ground + a 10x10 field of ellipsoids (every 5th followed by an exact duplicate with another
     material: ties inside one BVH leaf) + a unit sphere at (4,1,0) added 10 times with 10
@@ -86,9 +91,7 @@ def tie_scene(om, O, duplicates=True):
     duplicates=False drops every later copy: the frame where the FIRST object would win."""
     w, ow = om.HittableList.new(), O.World()
     rng = np.random.default_rng(20260117)
-    palette = [("lambertian", (0.8, 0.3, 0.2), 0.0, 0.0), ("metal", (0.7, 0.8, 0.9), 0.1, 0.0),
-               ("dielectric", (0.0, 0.0, 0.0), 0.0, 1.5), ("lambertian", (0.1, 0.6, 0.2), 0.0, 0.0),
-               ("metal", (0.9, 0.6, 0.3), 0.4, 0.0)]
+    palette = TIE_PALETTE
 
     def mat(k):
         kind, alb, fuzz, ior = palette[k % len(palette)]
@@ -126,6 +129,79 @@ def tie_scene(om, O, duplicates=True):
         m, m_ = mat(0)
         w += om.Parallelogram.new3points(p1, p2, p3, m); ow.add_parallelogram(p1, p2, p3, m_)
     return w, ow
+
+
+def cluster_world(om, O, per, side):
+    """Ground + side x side clusters of `per` nearly coincident spheres (centres 0.01 apart, radii
+    growing by 0.005), added in the order tests/cpp/tree_regimes.cpp uses, everything in f32.
+    The SAH builder keeps a cluster in one leaf, so `per` sets the records per leaf and
+    per * side^2 the record count: BVH2 trees that stay small enough for LDS while their record
+    indices pass the 11 bits of a direct leaf code -- which random_scene cannot give at any size."""
+    w, ow = om.HittableList.new(), O.World()
+    n = 0
+
+    def mat():
+        nonlocal n
+        kind, alb, fuzz, ior = TIE_PALETTE[n % len(TIE_PALETTE)]
+        n += 1
+        if kind == "lambertian":
+            return om.Material.new_lambertian(alb), O.material(kind, alb)
+        if kind == "metal":
+            return om.Material.new_metal_fuzz(alb, fuzz), O.material(kind, alb, fuzz=fuzz)
+        return om.Material.new_dielectric(ior), O.material(kind, ior=ior)
+
+    m, m_ = mat()
+    w += om.Sphere.new_with_radius((0., -1000., 0.), 1000., m); ow.add_sphere_radius((0., -1000., 0.), 1000., m_)
+    half = F(side) * F(0.5)
+    for a in range(side):
+        for b in range(side):
+            for k in range(per):
+                dk = F(0.01) * F(k)
+                c = (float((F(a) - half) + dk), float(F(0.2)), float((F(b) - half) - dk))
+                r = float(F(0.2) + F(0.005) * F(k))
+                m, m_ = mat()
+                w += om.Sphere.new_with_radius(c, r, m); ow.add_sphere_radius(c, r, m_)
+    return w, ow
+
+
+def _grid_world(grid_half, extras=True):
+    return lambda om, O: (om.random_scene(0x5EED, grid_half=grid_half, extras=extras),
+                          O.random_scene(0x5EED, grid_half=grid_half, extras=extras))
+
+
+def _cluster(per, side):
+    return lambda om, O: cluster_world(om, O, per, side)
+
+
+def _default_cameras(om, O, aspect):
+    return om.default_camera(aspect), O.default_camera(aspect)
+
+
+def _field_cameras(om, O, aspect):
+    """Looks down on the whole cluster field from (0,30,18): every pixel sees the field or the
+    ground, none the sky."""
+    args = ((0., 30., 18.), (0., 0., 0.), (0., 1., 0.), 32., aspect, 0., 35.)
+    return om.Camera.new(*args), O.camera(*args)
+
+
+# name (as printed by tests/cpp/tree_regimes.cpp) -> (world builder, camera builder): one world per
+# tree regime of the BVH2 / BVH4 / SBVH traversals; tests/test_tree_regimes.py pins which regime
+# each is in, tests/test_gpu_tree_regimes.py renders them.
+REGIME_WORLDS = {
+    "g0x": (_grid_world(0, extras=False), _default_cameras),    # ground only: no BVH2, the reference loop
+    "g0": (_grid_world(0), _default_cameras),                   # one node: a single leaf + an empty second child
+    "g11": (_grid_world(11), _default_cameras),                 # S-traced: LDS, direct codes, leaves <= 2
+    "g15": (_grid_world(15), _default_cameras),                 # the megakernel's staged SBVH at 92 % of its budget
+    "g16": (_grid_world(16), _default_cameras),                 # BVH2 and BVH4 in LDS at 96 % / 93 %; SBVH not staged
+    "g17": (_grid_world(17), _default_cameras),                 # first tree read through L2: direct codes, 1-record leaves
+    "g22": (_grid_world(22), _default_cameras),                 # L2, direct codes with `first` near the 11-bit limit
+    "g23": (_grid_world(23), _default_cameras),                 # first L2 tree with a leaf table
+    "g50x": (_grid_world(50, extras=False), _default_cameras),  # S-10k: L2 + table
+    "g91x": (_grid_world(91, extras=False), _default_cameras),  # >= 32768 prims: the max-leaf fallback tree
+    "c7x17": (_cluster(7, 17), _field_cameras),                 # LDS, direct codes, 7-record leaves, `first` up to 2016
+    "c7x18": (_cluster(7, 18), _field_cameras),                 # LDS + leaf table
+    "c8x17": (_cluster(8, 17), _field_cameras),                 # LDS + leaf table at 96 % of the budget, BVH4 at 100 %
+}
 
 
 def nan_normal_world(om, O):
