@@ -5,17 +5,36 @@ by default, --fixed-spp to take every sample), then save every display view (key
 the F12 save of main.rs:473-476.
 
     python examples/render_scene.py --width 1000 --height 666 --spp 200 --out out/
+    python examples/render_scene.py --width 1000 --height 666 --pick 500 400      # what is under a pixel
 """
 import argparse
 import os
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import raytracingoneweekend_amd as om  # noqa: E402
 from raytracingoneweekend_amd import _lib as L  # noqa: E402
+
+
+def pick(world, frozen, cam, W, H, x, y):
+    """The object under pixel (x, y): its centre ray from a pinhole at the camera origin (no lens
+    offset), built here on the host in f32, through FrozenHittableList.hit."""
+    F = np.float32
+    r = cam.raw
+    org, hor, ver, llc = (np.array(list(v), dtype=F) for v in (r.origin, r.horizontal, r.vertical, r.lower_left_corner))
+    u, v = (F(x) + F(0.5)) / F(W), F(1.0) - (F(y) + F(0.5)) / F(H)
+    d = llc + u * hor + v * ver - org
+    d = (d / np.sqrt((d * d).sum(dtype=F), dtype=F)).astype(F)
+    h = frozen.hit(org, d)
+    if h is None:
+        print(f"pixel ({x}, {y}): sky")
+        return
+    print(f"pixel ({x}, {y}): obj {h.obj}, t {h.t:.6g}, point {tuple(float(c) for c in h.point)}, {world.material_of(h.obj)}")
 
 
 def main():
@@ -32,12 +51,19 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default="out")
     ap.add_argument("--ppm", action="store_true", help="write PPM instead of BMP")
+    ap.add_argument("--pick", type=int, nargs=2, metavar=("X", "Y"),
+                    help="print the object id, t and material under the centre of pixel (X, Y) and exit (no render)")
     args = ap.parse_args()
 
     W, H = args.width, args.height
     world = om.random_scene_api(0x5EED, with_torus=args.torus)   # main.rs:37-100 through the API
     cam = om.Camera.new((13.0, 2.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 20.0, W / H, 0.1, 10.0)  # main.rs:136-142
     frozen = world.freeze(cam)
+    if args.pick:
+        if not (0 <= args.pick[0] < W and 0 <= args.pick[1] < H):
+            ap.error("--pick: the pixel is outside the frame")
+        pick(world, frozen, cam, W, H, *args.pick)
+        return
     pixels = om.PixelsBox.new(W * H)
     t0, credited = time.perf_counter(), 0
     for done in range(0, args.spp, args.per_call):

@@ -22,6 +22,7 @@
  *   om_material_*         Material::new_*                           materials.rs:27-38
  *   om_camera_new         Camera::new                               camera.rs:38-59
  *   om_upload_world       HittableList::freeze -> FrozenHittableList  hits.rs:87-89, 116-185
+ *   om_hit_rays*   FrozenHittableList::hit   hits.rs:270-334
  *   om_render / om_render_device   render_thread::render (all threads of main.rs:200-214)
  *                                                                   render_thread.rs:145-202
  *   om_pixel_stats        Pixel/Stats                               render_thread.rs:9-51
@@ -202,6 +203,9 @@ om_status om_world_marched_sdf_count(const om_world* w, uint32_t* n);
 /* counts[8] in type order: spheres, cubes, triangles, infinite_planes, parallelograms,
  * marched_spheres, marched_boxes, marched_torus (hits.rs:370-371) */
 om_status om_world_counts(const om_world* w, uint32_t counts[8]);
+/* HitRecord.material (hits.rs:16) of an obj id as om_hit / om_pixel_stats report it (global
+ * type-order index + 1).  Host only.  OM_ERR_INVALID for 0 (no hit) or an id past the last object. */
+om_status om_world_object_material(const om_world* w, uint32_t obj, om_material* out);
 /* Frozen per-primitive data, for cross-checks (layouts in DESIGN.md §4):
  * kind 0 sphere / 1 cube -> 32 floats (l2w, w2l); kind 2 triangle / 4 parallelogram -> 29 floats;
  * kind 7 torus -> 43 floats. */
@@ -229,6 +233,41 @@ om_status om_set_kernel(om_ctx* ctx, int32_t kernel);
  * runtime.  Prefer few calls per frame (om_progress reports progress inside a call). */
 om_status om_render(om_ctx* ctx, const om_camera* cam, const om_render_params* p, om_pixel_stats* stats,
                     om_counters* counters /* optional */);
+
+/* ---- closest-hit ray queries: FrozenHittableList::hit(ray, t_min, t_max) (hits.rs:270-334) ----
+ * One record per ray, the reference loop's answer for it, through the traversal, tie rule and
+ * HitRecord code the render kernels use for the ctx's kernel choice and uploaded world (rays with
+ * NaN or infinite components, which no camera produces, run the reference loop itself).
+ *   om_ray   the `Ray { orig, dir }` literal (ray.rs:5-8).  dir is used as given, never normalised
+ *            on the device.  The precondition is a unit direction (Ray::new's invariant, ray.rs:12,
+ *            which every ray the renderer traces meets): the march's step and the traversal's
+ *            culls assume it, and results for non-unit directions are unspecified.
+ *   om_hit   HitRecord (hits.rs:11-17) without the material (om_world_object_material gives it):
+ *            obj is the id convention of om_pixel_stats (global type-order index + 1, 0 = no
+ *            hit); normal is HitRecord.normal as the reference leaves it (not normalised for
+ *            cubes, traced.rs:293-296; flipped against the ray for planes).  A miss is fully
+ *            defined: obj = 0, t = +inf, point = normal = 0.  Rays with NaN or infinite
+ *            components give what the reference loop gives for them.
+ *   om_query_params  one (tmin, tmax, march_steps) per call; reserved must be 0.
+ * n == 0 is OM_OK and launches nothing; a null pointer, reserved != 0 or a NaN tmin / tmax is
+ * OM_ERR_INVALID; a query before om_upload_world is OM_ERR_STATE.  With counting on, a query adds
+ * n to om_counters.segments and its prim_tests / pre_tests / march_steps; samples, credited and
+ * the om_progress word are untouched.  Like renders, queries on one ctx are driven from one
+ * stream at a time. */
+typedef struct om_ray { float orig[3]; float dir[3]; } om_ray;                  /* 24 B, ray.rs:5-8 */
+typedef struct om_hit { float t; float point[3]; float normal[3]; uint32_t obj; } om_hit; /* 32 B, hits.rs:11-17 */
+typedef struct om_query_params { float tmin, tmax; uint32_t march_steps; uint32_t reserved; } om_query_params;
+/* Device form: dev_rays / dev_hits are device memory (n records each) on ctx's device;
+ * asynchronous on `stream` (NULL = ctx's own stream). */
+om_status om_hit_rays_device(om_ctx* ctx, const om_query_params* q, const om_ray* dev_rays, uint32_t n, om_hit* dev_hits,
+                             void* stream);
+/* Host form, synchronous: copies through staging buffers the ctx owns (grown on demand, reused);
+ * the copies run at DMA speed when the caller's buffers are page-locked (om_host_register). */
+om_status om_hit_rays(om_ctx* ctx, const om_query_params* q, const om_ray* rays, uint32_t n, om_hit* hits);
+/* Workgroups of the largest query launch on ctx's device (the kernel is persistent: a workgroup
+ * stages the tree once and loops over blocks of OM_QUERY_BLOCK rays); 0 on error. */
+#define OM_QUERY_BLOCK 512
+uint32_t om_query_max_grid(om_ctx* ctx);
 /* Page-lock a caller-owned host buffer (e.g. the framebuffer) so om_render's copies run as
  * DMA at full PCIe speed; the buffer must stay allocated until om_host_unregister. */
 om_status om_host_register(void* p, size_t bytes);

@@ -268,6 +268,12 @@ public:
         return *this;
     }
     void clear() { check(om_world_clear(w_)); }
+    // HitRecord.material (hits.rs:16) of an obj id as hit() reports it; throws for 0 or an id past the end
+    Material material_of(uint32_t obj) const {
+        Material m;
+        check(om_world_object_material(w_, obj, &m.raw));
+        return m;
+    }
 
     // hits.rs:87-89.  The camera only fed the reference's camera hash (out of scope,
     // DESIGN.md §9); the frozen world lives in HBM on `device`.
@@ -303,6 +309,25 @@ public:
     void set_kernel(int32_t kernel) { check(om_set_kernel(ctx_, kernel), ctx_); }
     void set_pipeline(int32_t pipeline) { check(om_set_pipeline(ctx_, pipeline), ctx_); }
     om_ctx* ctx() const { return ctx_; }
+
+    // FrozenHittableList::hit (hits.rs:270-334): the closest hit of one ray; false = None, and
+    // `rec` is then the miss record (obj 0, t inf).  `dir` is used as given; a unit direction is
+    // the precondition (Ray::new, ray.rs:12).  The material is HittableList::material_of(rec.obj).
+    bool hit(const Vec3& orig, const Vec3& dir, float t_min, float t_max, om_hit& rec, uint32_t march_steps = 1024) const {
+        om_ray r;
+        for (int k = 0; k < 3; ++k) { r.orig[k] = orig.e[k]; r.dir[k] = dir.e[k]; }
+        const om_query_params q{t_min, t_max, march_steps, 0u};
+        check(om_hit_rays(ctx_, &q, &r, 1u, &rec), ctx_);
+        return rec.obj != 0u;
+    }
+    // The same for a batch: one om_hit per ray, in order (om_hit_rays; page-lock large buffers
+    // with om_host_register for DMA-speed copies).
+    std::vector<om_hit> hit_rays(const std::vector<om_ray>& rays, float t_min, float t_max, uint32_t march_steps = 1024) const {
+        std::vector<om_hit> hits(rays.size());
+        const om_query_params q{t_min, t_max, march_steps, 0u};
+        check(om_hit_rays(ctx_, &q, rays.data(), (uint32_t)rays.size(), hits.data()), ctx_);
+        return hits;
+    }
 
 private:
     om_ctx* ctx_ = nullptr;

@@ -46,6 +46,25 @@ class om_counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "segments", "prim_tests", "pre_tests", "march_steps", "credited")]
 
 
+class om_ray(C.Structure):                     # ray.rs:5-8, 24 B
+    _fields_ = [("orig", C.c_float * 3), ("dir", C.c_float * 3)]
+
+
+class om_hit(C.Structure):                     # hits.rs:11-17 without the material, 32 B
+    _fields_ = [("t", C.c_float), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("obj", C.c_uint32)]
+
+
+class om_query_params(C.Structure):
+    _fields_ = [("tmin", C.c_float), ("tmax", C.c_float), ("march_steps", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# numpy views of om_ray / om_hit
+RAY_DTYPE = np.dtype([("orig", "<f4", (3,)), ("dir", "<f4", (3,))])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("point", "<f4", (3,)), ("normal", "<f4", (3,)), ("obj", "<u4")])
+assert RAY_DTYPE.itemsize == 24 and HIT_DTYPE.itemsize == 32
+OM_QUERY_BLOCK = 512
+
+
 # om_sdf_op (include/ottomarcher.h): one op of a user marched object's SDF program
 SDF_OP_DTYPE = np.dtype([("op", "<i4"), ("a", "<f4", 7)])
 SDF_OPS = {"sphere": 1, "box": 2, "torus": 3, "union": 4, "intersect": 5, "subtract": 6, "round": 7}
@@ -93,6 +112,7 @@ EXPORTS = [
     "om_multi_destroy", "om_multi_transport", "om_multi_ctx", "om_multi_upload_world", "om_multi_render",
     "om_multi_last_error", "om_progress", "om_reset_progress", "om_host_register", "om_host_unregister",
     "om_multi_render_host", "om_multi_gather", "om_multi_reset", "om_rccl_library",
+    "om_hit_rays_device", "om_hit_rays", "om_world_object_material", "om_query_max_grid",
 ]
 OM_COMM_ID_BYTES = 128
 OM_TRANSPORT_RCCL, OM_TRANSPORT_LOCAL = 0, 1
@@ -207,6 +227,10 @@ def _load():
         "om_multi_reset": (None, [vp]),
         "om_rccl_library": (st, [C.c_char_p, C.c_uint32, C.POINTER(C.c_int32)]),
         "om_comm_info": (st, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "om_hit_rays_device": (st, [vp, C.POINTER(om_query_params), vp, C.c_uint32, vp, vp]),
+        "om_hit_rays": (st, [vp, C.POINTER(om_query_params), vp, C.c_uint32, vp]),
+        "om_world_object_material": (st, [vp, C.c_uint32, mp]),
+        "om_query_max_grid": (C.c_uint32, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -24,8 +24,11 @@ from ._lib import check, f3, fptr, lib
 __all__ = [
     "Material", "Mat4x4", "m4x4", "Camera", "Sphere", "Cube", "Triangle", "Parallelogram", "InfinitePlane",
     "MarchedSphere", "MarchedBox", "MarchedTorus", "MarchedSdf", "HittableList", "FrozenHittableList", "PixelsBox", "render",
-    "RenderStats",
+    "RenderStats", "HitRecord", "HIT_DTYPE", "RAY_DTYPE",
 ]
+
+HIT_DTYPE = L.HIT_DTYPE     # om_hit: t, point, normal, obj (hits.rs:11-17)
+RAY_DTYPE = L.RAY_DTYPE     # om_ray: orig, dir (ray.rs:5-8)
 
 
 # ---------------------------------------------------------------- materials.rs
@@ -304,6 +307,13 @@ class HittableList:
         check(lib.om_world_export(self._w, int(kind), int(index), fptr(out), n))
         return np.array(list(out), dtype=np.float32)
 
+    def material_of(self, obj):
+        """HitRecord.material (hits.rs:16) of an obj id as hit() / om_pixel_stats report it
+        (global type-order index + 1); raises for 0 or an id past the last object."""
+        raw = L.om_material()
+        check(lib.om_world_object_material(self._w, int(obj), C.byref(raw)))
+        return Material(raw)
+
     def freeze(self, cam=None, device=0, kernel="auto", pipeline="auto"):
         """hits.rs:87-89: snapshot to device memory (the camera is unused: the camera hash is out of scope)."""
         return FrozenHittableList(self, device=device, kernel=kernel, pipeline=pipeline)
@@ -343,6 +353,91 @@ class FrozenHittableList:
         c = L.om_counters()
         check(lib.om_get_counters(self._ctx, C.byref(c)), self._ctx)
         return {n: getattr(c, n) for n, _ in L.om_counters._fields_}
+
+    def hit(self, orig, dir, tmin=0.001, tmax=100.0, march_steps=1024):
+        """FrozenHittableList::hit (hits.rs:270-334) for one ray -> HitRecord or None.  `dir` is
+        used as given; a unit direction is the precondition (Ray::new, ray.rs:12)."""
+        rays = np.array([list(orig) + list(dir)], dtype=np.float32)
+        h = self.hit_rays(rays, tmin, tmax, march_steps)[0]
+        if h["obj"] == 0:
+            return None
+        return HitRecord(float(h["t"]), h["point"].copy(), h["normal"].copy(), int(h["obj"]))
+
+    def hit_rays(self, rays, tmin=0.001, tmax=100.0, march_steps=1024, out=None, stream=None):
+        """Closest hits of a batch of rays (om_hit_rays / om_hit_rays_device).
+
+        `rays`: an (n, 6) float32 array (orig, dir per row; or an n-vector of RAY_DTYPE) -> an
+        n-vector of HIT_DTYPE (obj 0, t inf on a miss), synchronous; or a torch ROCm tensor of
+        that shape on this world's device -> an (n, 8) float32 tensor of om_hit records on the
+        device (column 7 holds the obj bits: `.view(torch.int32)`), traced in place with no host
+        copy, asynchronously, in the order of `stream` (a non-null hipStream_t) or, by default, of
+        torch's current stream on that device: the query runs after the work already queued there
+        (the ops that made `rays`) and before what is queued afterwards (the readers of the result).
+        When torch's current stream is the null stream, whose handle the C entry point would read as
+        "the ctx's own stream", the launch goes to a side stream of this object that is ordered
+        with the null stream by events on both sides."""
+        q = L.om_query_params(float(tmin), float(tmax), int(march_steps), 0)
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6 \
+                    or not rays.is_contiguous():
+                raise ValueError("hit_rays: need a contiguous (n, 6) float32 tensor on the device")
+            if rays.device.index != int(self.device):
+                raise ValueError(f"hit_rays: rays are on {rays.device}, the world is on device {self.device}")
+            n = rays.shape[0]
+            if out is None:
+                out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+            elif not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() \
+                    or out.device != rays.device:
+                raise ValueError("hit_rays: out must be a contiguous (n, 8) float32 tensor on the rays' device")
+            if stream is not None and int(stream) == 0:
+                raise ValueError("hit_rays: stream 0 is the ctx's own stream to the library; pass a stream or none")
+            cur = side = None
+            if stream is None:
+                cur = torch.cuda.current_stream(rays.device)
+                stream = cur.cuda_stream
+                if stream == 0:                                   # torch's null stream: order a side stream with it
+                    if getattr(self, "_torch_side", None) is None:
+                        self._torch_side = torch.cuda.Stream(device=rays.device)
+                    side = self._torch_side
+                    side.wait_stream(cur)
+                    stream = side.cuda_stream
+            try:
+                check(lib.om_hit_rays_device(self._ctx, C.byref(q), C.c_void_p(rays.data_ptr()), n,
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
+            finally:
+                if side is not None:
+                    rays.record_stream(side)                      # the allocator must not reuse them under the kernel
+                    out.record_stream(side)
+                    cur.wait_stream(side)
+            return out
+        a = np.ascontiguousarray(rays)
+        if a.dtype == L.RAY_DTYPE:
+            a = a.reshape(-1)
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 6:
+                raise ValueError("hit_rays: need an (n, 6) float32 array")
+        n = a.shape[0]
+        hits = np.empty(n, dtype=L.HIT_DTYPE)
+        check(lib.om_hit_rays(self._ctx, C.byref(q), a.ctypes.data_as(C.c_void_p), n, hits.ctypes.data_as(C.c_void_p)),
+              self._ctx)
+        return hits
+
+    def query_max_grid(self):
+        """Workgroups of the largest query launch on this device (om_query_max_grid)."""
+        return int(lib.om_query_max_grid(self._ctx))
+
+
+class HitRecord:
+    """hits.rs:11-17: t, point, normal and the obj id (HittableList.material_of gives the material)."""
+    __slots__ = ("t", "point", "normal", "obj")
+
+    def __init__(self, t, point, normal, obj):
+        self.t, self.point, self.normal, self.obj = t, point, normal, obj
+
+    def __repr__(self):
+        return f"HitRecord(t={self.t}, point={tuple(self.point)}, normal={tuple(self.normal)}, obj={self.obj})"
 
 
 # ---------------------------------------------------------------- render_thread.rs

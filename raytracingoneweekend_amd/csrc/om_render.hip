@@ -33,6 +33,8 @@
 using namespace omd;
 
 static_assert(sizeof(om_pixel_stats) == 40, "om_pixel_stats layout");
+static_assert(sizeof(om_ray) == 24 && sizeof(om_hit) == 32 && sizeof(om_query_params) == 16, "query record layouts");
+static_assert(OM_QUERY_BLOCK == 512, "OM_QUERY_BLOCK is the wavefront workgroup size");
 static_assert(sizeof(OmAffineTest) == 64 && sizeof(OmBvhNode) == 32, "layout");
 
 namespace {
@@ -287,11 +289,13 @@ struct om_ctx {
     omw::Buffers wf;
     unsigned long long* progress_host = nullptr;   // om_progress: pinned host word (null: progress off)
     DevBuf frame_list;                  // tile-ordered pixel list of the full frame (wavefront path)
+    DevBuf query_rays, query_hits;      // om_hit_rays staging (grown on demand, reused)
     uint32_t frame_w = 0, frame_h = 0;
     ~om_ctx() {
         for (auto& b : scene_bufs) b.release();
         for (auto& j : jitters) j.buf.release();
         counters.release(); stats.release(); pixels.release(); frame_list.release();
+        query_rays.release(); query_hits.release();
         view_scratch.release(); view_rgb.release(); tile_off.release(); tile_idx.release(); tile_tnear.release();
         wf.release();
         timer.release();
@@ -438,6 +442,13 @@ om_status ensure_tile_lists(om_ctx* c, const om_camera* cam, uint32_t W, uint32_
     return OM_OK;
 }
 
+// omw::Launch::trace_mode of a resolved (non-AUTO) OM_KERNEL_* choice
+int wf_trace_mode(int mode) {
+    return mode == OM_KERNEL_BRUTE ? MODE_BRUTE : mode == OM_KERNEL_CULLED ? MODE_CULLED
+         : mode == OM_KERNEL_BVH ? MODE_BVH : mode == OM_KERNEL_BVH2 ? 6
+         : mode == OM_KERNEL_BVH4 ? 8 : MODE_SBVH_LDS;
+}
+
 om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_pixel_stats* dev_stats,
                  const uint32_t* dev_pixels, uint32_t n_pixels, hipStream_t stream) {
     // samples_per_pixel = 0: render()'s pass loop never runs (render_thread.rs:176), Stats untouched
@@ -508,9 +519,7 @@ om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_
                 L.tile_tnear = (const float*)c->tile_tnear.p;
             }
         }
-        L.trace_mode = mode == OM_KERNEL_BRUTE ? MODE_BRUTE : mode == OM_KERNEL_CULLED ? MODE_CULLED
-                     : mode == OM_KERNEL_BVH ? MODE_BVH : mode == OM_KERNEL_BVH2 ? 6
-                     : mode == OM_KERNEL_BVH4 ? 8 : MODE_SBVH_LDS;
+        L.trace_mode = wf_trace_mode(mode);
         if (dev_pixels) {
             L.pixels = dev_pixels; L.n_pixels = n_pixels; L.stats_by_pixel = false;
         } else {
@@ -689,6 +698,63 @@ om_status om_render(om_ctx* c, const om_camera* cam, const om_render_params* p, 
     OM_HIP(c, hipStreamSynchronize(c->stream));
     if (counters) return om_get_counters(c, counters);
     return OM_OK;
+}
+
+// ---- closest-hit ray queries (FrozenHittableList::hit, hits.rs:270-334) ----
+static om_status validate_query(om_ctx* c, const om_query_params* q, const void* rays, uint32_t n, const void* hits) {
+    if (!c) return set_err(nullptr, OM_ERR_INVALID, "om_hit_rays: null ctx");
+    if (!q) return set_err(c, OM_ERR_INVALID, "om_hit_rays: null params");
+    if (q->reserved != 0u) return set_err(c, OM_ERR_INVALID, "om_hit_rays: reserved must be 0");
+    if (std::isnan(q->tmin) || std::isnan(q->tmax)) return set_err(c, OM_ERR_INVALID, "om_hit_rays: tmin/tmax is NaN");
+    if (!c->have_world) return set_err(c, OM_ERR_STATE, "om_upload_world must precede ray queries");
+    if (n && (!rays || !hits)) return set_err(c, OM_ERR_INVALID, "om_hit_rays: null rays/hits");
+    return OM_OK;
+}
+
+om_status om_hit_rays_device(om_ctx* c, const om_query_params* q, const om_ray* dev_rays, uint32_t n, om_hit* dev_hits,
+                             void* stream) {
+    om_status s = validate_query(c, q, dev_rays, n, dev_hits);
+    if (s) return s;
+    if (n == 0) return OM_OK;
+    OM_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (!c->counters.p) {
+        if ((s = ensure(c, c->counters, OMC_SLOTS * sizeof(unsigned long long))) != OM_OK) return s;
+        OM_HIP(c, hipMemsetAsync(c->counters.p, 0, OMC_SLOTS * sizeof(unsigned long long), st));
+    }
+    c->last_stream = st;
+    int mode = c->kernel;
+    if (mode == OM_KERNEL_AUTO) mode = OM_KERNEL_BVH2;
+    omw::Query Q;
+    Q.S = c->scene;
+    Q.tmin = q->tmin; Q.tmax = q->tmax; Q.march_steps = q->march_steps;
+    Q.rays = dev_rays; Q.hits = dev_hits; Q.n = n;
+    Q.counters = (unsigned long long*)c->counters.p;
+    Q.count = c->count_work;
+    Q.trace_mode = wf_trace_mode(mode);
+    const hipError_t e = omw::query(Q, st);
+    if (e != hipSuccess) return set_err(c, OM_ERR_DEVICE, std::string("om_hit_rays_device: ") + hipGetErrorString(e));
+    return OM_OK;
+}
+
+om_status om_hit_rays(om_ctx* c, const om_query_params* q, const om_ray* rays, uint32_t n, om_hit* hits) {
+    om_status s = validate_query(c, q, rays, n, hits);
+    if (s) return s;
+    if (n == 0) return OM_OK;
+    OM_HIP(c, hipSetDevice(c->device));
+    if ((s = ensure(c, c->query_rays, (size_t)n * sizeof(om_ray))) != OM_OK) return s;
+    if ((s = ensure(c, c->query_hits, (size_t)n * sizeof(om_hit))) != OM_OK) return s;
+    OM_HIP(c, hipMemcpyAsync(c->query_rays.p, rays, (size_t)n * sizeof(om_ray), hipMemcpyHostToDevice, c->stream));
+    if ((s = om_hit_rays_device(c, q, (const om_ray*)c->query_rays.p, n, (om_hit*)c->query_hits.p, c->stream)) != OM_OK) return s;
+    OM_HIP(c, hipMemcpyAsync(hits, c->query_hits.p, (size_t)n * sizeof(om_hit), hipMemcpyDeviceToHost, c->stream));
+    OM_HIP(c, hipStreamSynchronize(c->stream));
+    return OM_OK;
+}
+
+uint32_t om_query_max_grid(om_ctx* c) {
+    if (!c) { set_err(nullptr, OM_ERR_INVALID, "om_query_max_grid: null ctx"); return 0u; }
+    if (hipSetDevice(c->device) != hipSuccess) { set_err(c, OM_ERR_DEVICE, "om_query_max_grid: hipSetDevice"); return 0u; }
+    return omw::query_max_grid();
 }
 
 om_status om_host_register(void* p, size_t bytes) {

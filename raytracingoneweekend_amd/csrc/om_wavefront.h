@@ -97,4 +97,20 @@ struct Launch {
 // Renders P.sample_count samples of every listed pixel; returns 0 or a HIP error text.
 hipError_t render(Buffers& B, const Launch& L, hipStream_t stream, std::string& err);
 
+// One batch of closest-hit ray queries (om_hit_rays_device).
+struct Query {
+    OmSceneDev S;
+    float tmin, tmax;
+    uint32_t march_steps;
+    const om_ray* rays;          // device, n records
+    om_hit* hits;                // device, n records
+    uint32_t n;
+    unsigned long long* counters;
+    bool count;
+    int trace_mode;              // as Launch::trace_mode
+};
+// Traces Q.n rays in one persistent launch on `stream` (at most query_max_grid() workgroups).
+hipError_t query(const Query& Q, hipStream_t stream);
+uint32_t query_max_grid();       // on the current device
+
 }  // namespace omw

@@ -24,6 +24,7 @@
 #include "om_wavefront.h"
 
 #include <algorithm>
+#include <type_traits>
 
 #include "om_device.h"
 #include "om_trace.h"
@@ -769,6 +770,102 @@ void k_tail(OmSceneDev S, OmParamsDev P, Seg G, Queue in,
     }
 }
 
+// ---------------------------------------------------------------- ray queries
+// k_query: FrozenHittableList::hit (hits.rs:270-334) for n caller-given rays, one om_hit each: the
+// trace and the HitRecord code of the bounce kernels, with no camera, shading or queue (DESIGN.md
+// §5.15).  Persistent: at most a resident grid of workgroups, each staging the scene once
+// (stage_scene's tree copy is the cost floor of a small launch) and then taking the ray blocks
+// b, b + gridDim.x, ...  Lanes past n in the last block only skip the trace; nothing after the
+// staging synchronises the workgroup.
+// The direction is used as given (the `Ray { orig, dir }` literal): a unit direction is the
+// documented precondition (Ray::new, ray.rs:12); the march's step and the traversal's culls
+// assume it, and results for non-unit directions are unspecified.  Non-finite rays take the
+// reference loop (see the ray loop).
+// Rays (24 B) and hits (32 B) are streamed once each with the non-temporal hint, like the path
+// queues, so they do not evict nodes and leaf records from the vector L1; buffers aligned to
+// 8 / 16 B (wave-uniform test) move as dwordx2 / dwordx4.
+__device__ __forceinline__ void load_query_ray(const om_ray* __restrict__ rays, uint64_t i, F3& o, F3& d) {
+    const float* r = (const float*)(rays + i);
+    if (((uintptr_t)rays & 7u) == 0u) {
+        const float2* r2 = (const float2*)r;
+        float2 a, b, c;
+        a.x = __builtin_nontemporal_load(&r2[0].x); a.y = __builtin_nontemporal_load(&r2[0].y);
+        b.x = __builtin_nontemporal_load(&r2[1].x); b.y = __builtin_nontemporal_load(&r2[1].y);
+        c.x = __builtin_nontemporal_load(&r2[2].x); c.y = __builtin_nontemporal_load(&r2[2].y);
+        o = f3(a.x, a.y, b.x); d = f3(b.y, c.x, c.y);
+    } else {
+        o = f3(__builtin_nontemporal_load(r), __builtin_nontemporal_load(r + 1), __builtin_nontemporal_load(r + 2));
+        d = f3(__builtin_nontemporal_load(r + 3), __builtin_nontemporal_load(r + 4), __builtin_nontemporal_load(r + 5));
+    }
+}
+__device__ __forceinline__ void store_query_hit(om_hit* __restrict__ hits, uint64_t i, float t, F3 p, F3 n, uint32_t obj) {
+    if (((uintptr_t)hits & 15u) == 0u) {
+        float4* h = (float4*)(hits + i);
+        st4(h, make_float4(t, p.x, p.y, p.z));
+        st4(h + 1, make_float4(n.x, n.y, n.z, __uint_as_float(obj)));
+    } else {
+        float* h = (float*)(hits + i);
+        __builtin_nontemporal_store(t, h);
+        __builtin_nontemporal_store(p.x, h + 1); __builtin_nontemporal_store(p.y, h + 2); __builtin_nontemporal_store(p.z, h + 3);
+        __builtin_nontemporal_store(n.x, h + 4); __builtin_nontemporal_store(n.y, h + 5); __builtin_nontemporal_store(n.z, h + 6);
+        __builtin_nontemporal_store(__uint_as_float(obj), h + 7);
+    }
+}
+
+// A lane of the persistent k_query counts over every block its workgroup takes, up to 2^32 / (grid x
+// 512) rays of any cost, so its totals and the wave's sum are kept in 64 bits (WorkT's u32 fields
+// hold one ray's counts); a render kernel's lane counts a bounded number of segments and sums in 32.
+__device__ __forceinline__ void flush_counter64(unsigned long long* ctr, int slot, unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (__lane_id() == 0 && v) atomicAdd(&ctr[slot], v);
+}
+
+template <int TR, bool MARCH, bool USER, bool COUNT>
+__global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_query(OmSceneDev S, OmParamsDev P, const om_ray* __restrict__ rays,
+                                                uint32_t n, om_hit* __restrict__ hits,
+                                                unsigned long long* __restrict__ counters) {
+    const Tracer T = stage_scene<TR>(S);
+    unsigned long long segs = 0, n_prim = 0, n_pre = 0, n_march = 0;
+    const uint32_t nblocks = (uint32_t)(((uint64_t)n + kBlk - 1u) / kBlk);
+    for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {      // (b + gridDim.x <= 2^23 + 2^23: no wrap)
+        const uint64_t i = (uint64_t)b * kBlk + threadIdx.x;
+        if (i >= n) continue;
+        WorkT<COUNT> w;                                          // this ray's work
+        F3 o, d;
+        load_query_ray(rays, i, o, d);
+        float closest;
+        int best;
+        // The tree traversals answer a non-finite ray with nonfinite_hit's closed form, which is the
+        // reference loop's answer when a component is NaN but not always when one is infinite (an
+        // infinite root is rejected where a NaN root is accepted).  A query can be handed any ray,
+        // so such rays (never a whole wave in practice) run the reference loop itself.
+        constexpr bool kShortcut = TR == TR_BVH2_LDS || TR == TR_BVH2_GLOBAL || TR == TR_BVH4_LDS || TR == TR_BVH4_GLOBAL;
+        if (kShortcut && !isfinite(o.x + o.y + o.z + d.x + d.y + d.z)) {
+            closest = P.tmax;
+            best = traced_brute<false>(S, o, d, P.tmin, closest, w);
+        } else {
+            best = trace<TR, false>(S, P, T, o, d, closest, w);
+        }
+        if (MARCH) {                                             // trace<TR, true>'s march, once for both branches
+            float tm;
+            const int mg = march(S, o, d, P.tmin, P.tmax, closest, P.march_steps, tm, w);
+            if (mg >= 0) { best = mg; closest = tm; }
+        }
+        if (COUNT) { segs++; n_prim += w.prim; n_pre += w.pre; n_march += w.march; }
+        F3 point = f3(0.0f, 0.0f, 0.0f), normal = point;
+        if (best >= 0) finalize<MARCH, USER>(S, best, o, d, P.tmin, closest, point, normal);
+        else closest = INFINITY;
+        store_query_hit(hits, i, closest, point, normal, (uint32_t)(best + 1));
+    }
+    if (COUNT) {
+        flush_counter64(counters, OMC_SEGMENTS, segs);
+        flush_counter64(counters, OMC_PRIM_TESTS, n_prim);
+        flush_counter64(counters, OMC_PRE_TESTS, n_pre);
+        flush_counter64(counters, OMC_MARCH, n_march);
+    }
+}
+
 // ---------------------------------------------------------------- accumulate
 // Adaptive batches (ad.list): lane kk owns live-list entry kk, and a pixel that is still live after
 // the batch, with samples of the call left, is appended to the stream's next list (one ballot and
@@ -1034,6 +1131,53 @@ hipError_t ensure_events(Buffers& B, size_t n) {
     return hipSuccess;
 }
 
+// The closest-hit variant (TR_*) of a ctx's kernel choice (Launch::trace_mode) for the uploaded
+// world: renders and ray queries share it.
+int pick_trace(int trace_mode, const OmSceneDev& S) {
+    int tr = trace_mode == TR_SBVH_LDS ? TR_SBVH_GLOBAL : trace_mode;
+    if (tr == TR_BVH4_LDS) tr = S.n_b4nodes == 0 ? TR_BVH2_LDS : (S.b4_lds_bytes ? TR_BVH4_LDS : TR_BVH4_GLOBAL);
+    // an empty BVH2 (no bounded sphere/cube: marched-only worlds, C2) takes the reference loop
+    // when the old BVH holds at most one leaf: TR_BVH's 64-entry stack lives in scratch memory,
+    // which every k_march / k_tail wave would then carry for nothing (C2: 1785 vs 1649, r02_v8)
+    if (tr == TR_BVH2_LDS)
+        tr = S.n_b2nodes == 0 ? (S.n_bvh_nodes <= 1u ? TR_BRUTE : TR_BVH) : (S.b2_lds_bytes ? TR_BVH2_LDS : TR_BVH2_GLOBAL);
+    switch (tr) {
+        case TR_BRUTE: case TR_CULLED: case TR_BVH: case TR_SBVH_GLOBAL: case TR_BVH2_LDS: case TR_BVH4_LDS: case TR_BVH4_GLOBAL:
+            return tr;
+        default: return TR_BVH2_GLOBAL;
+    }
+}
+// dynamic LDS bytes of a workgroup that stages variant `tr` (stage_scene's [stack][nodes][leaf table])
+uint32_t trace_lds(int tr, const OmSceneDev& S) {
+    return tr == TR_BVH2_LDS ? stack_bytes<TR_BVH2_LDS>(S) + b2_stage_bytes(S)
+         : tr == TR_BVH2_GLOBAL ? stack_bytes<TR_BVH2_GLOBAL>(S) + hyb_nodes(S) * (uint32_t)sizeof(OmBvh2NodeH)
+         : tr == TR_BVH4_LDS ? stack_bytes<TR_BVH4_LDS>(S) + S.b4_lds_bytes
+         : tr == TR_BVH4_GLOBAL ? stack_bytes<TR_BVH4_GLOBAL>(S) + hyb4_nodes(S) * (uint32_t)sizeof(OmBvh4NodeH)
+         : 0u;
+}
+// f(std::integral_constant<int, TR>) for a variant pick_trace returned
+template <class F>
+void with_tr(int tr, F f) {
+    switch (tr) {
+        case TR_BRUTE: f(std::integral_constant<int, TR_BRUTE>{}); break;
+        case TR_CULLED: f(std::integral_constant<int, TR_CULLED>{}); break;
+        case TR_BVH: f(std::integral_constant<int, TR_BVH>{}); break;
+        case TR_SBVH_GLOBAL: f(std::integral_constant<int, TR_SBVH_GLOBAL>{}); break;
+        case TR_BVH2_LDS: f(std::integral_constant<int, TR_BVH2_LDS>{}); break;
+        case TR_BVH4_LDS: f(std::integral_constant<int, TR_BVH4_LDS>{}); break;
+        case TR_BVH4_GLOBAL: f(std::integral_constant<int, TR_BVH4_GLOBAL>{}); break;
+        default: f(std::integral_constant<int, TR_BVH2_GLOBAL>{}); break;
+    }
+}
+
+template <int TR, bool MARCH, bool USER>
+void launch_query(const Query& Q, const OmParamsDev& P, uint32_t grid, uint32_t lds, hipStream_t st) {
+    if (Q.count)
+        hipLaunchKernelGGL((k_query<TR, MARCH, USER, true>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.n, Q.hits, Q.counters);
+    else
+        hipLaunchKernelGGL((k_query<TR, MARCH, USER, false>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.n, Q.hits, Q.counters);
+}
+
 }  // namespace
 
 // Schedules:
@@ -1099,13 +1243,7 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
     (void)hipGetDevice(&dev);
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    int tr = L.trace_mode == TR_SBVH_LDS ? TR_SBVH_GLOBAL : L.trace_mode;
-    if (tr == TR_BVH4_LDS) tr = L.S.n_b4nodes == 0 ? TR_BVH2_LDS : (L.S.b4_lds_bytes ? TR_BVH4_LDS : TR_BVH4_GLOBAL);
-    // an empty BVH2 (no bounded sphere/cube: marched-only worlds, C2) takes the reference loop
-    // when the old BVH holds at most one leaf: TR_BVH's 64-entry stack lives in scratch memory,
-    // which every k_march / k_tail wave would then carry for nothing (C2: 1785 vs 1649, r02_v8)
-    if (tr == TR_BVH2_LDS)
-        tr = L.S.n_b2nodes == 0 ? (L.S.n_bvh_nodes <= 1u ? TR_BRUTE : TR_BVH) : (L.S.b2_lds_bytes ? TR_BVH2_LDS : TR_BVH2_GLOBAL);
+    const int tr = pick_trace(L.trace_mode, L.S);
     // segments, a multiple of the tail grouping: 4096 lanes per CU (8 workgroups of 512) for
     // traced worlds whose BVH2 sits in LDS, 8192 for marched worlds and L2-resident trees
     const bool march = (L.S.n_msph + L.S.n_mbox + L.S.n_mtor + L.S.n_msdf) != 0u;
@@ -1120,11 +1258,7 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
     const uint32_t segcap = seg_capacity(max_paths, nseg);
     hipError_t e = grow(B, (uint64_t)nseg * segcap, (depth_cap + 1u) * nseg, (int)ns);
     if (e != hipSuccess) { err = "wavefront buffer allocation failed"; return e; }
-    const uint32_t lds = tr == TR_BVH2_LDS ? stack_bytes<TR_BVH2_LDS>(L.S) + b2_stage_bytes(L.S)
-                       : tr == TR_BVH2_GLOBAL ? stack_bytes<TR_BVH2_GLOBAL>(L.S) + hyb_nodes(L.S) * (uint32_t)sizeof(OmBvh2NodeH)
-                       : tr == TR_BVH4_LDS ? stack_bytes<TR_BVH4_LDS>(L.S) + L.S.b4_lds_bytes
-                       : tr == TR_BVH4_GLOBAL ? stack_bytes<TR_BVH4_GLOBAL>(L.S) + hyb4_nodes(L.S) * (uint32_t)sizeof(OmBvh4NodeH)
-                       : 0u;
+    const uint32_t lds = trace_lds(tr, L.S);
     Gen R;
     R.C = L.C; R.jitter = L.jitter; R.stats = L.stats; R.pixels = L.pixels; R.n_pixels = n_px;
     R.by_pixel = L.stats_by_pixel ? 1u : 0u;
@@ -1194,16 +1328,9 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
         }
         R.batch = b;
         R.ad = ad;
-        switch (tr) {
-            case TR_BRUTE: launches += run_tr<TR_BRUTE>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds); break;
-            case TR_CULLED: launches += run_tr<TR_CULLED>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds); break;
-            case TR_BVH: launches += run_tr<TR_BVH>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds); break;
-            case TR_SBVH_GLOBAL: launches += run_tr<TR_SBVH_GLOBAL>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds); break;
-            case TR_BVH2_LDS: launches += run_tr<TR_BVH2_LDS>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds); break;
-            case TR_BVH4_LDS: launches += run_tr<TR_BVH4_LDS>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds); break;
-            case TR_BVH4_GLOBAL: launches += run_tr<TR_BVH4_GLOBAL>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds); break;
-            default: launches += run_tr<TR_BVH2_GLOBAL>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds); break;
-        }
+        with_tr(tr, [&](auto t) {
+            launches += run_tr<decltype(t)::value>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds);
+        });
         // accumulates in batch order: fixed spp needs it (Stats::add in sample order); an adaptive
         // stream's pixels are its own, so there it only keeps the streams in step and the progress
         // copies in order (unchained streams measured the same: 49.3 vs 49.2 ms per frame, r05_p6)
@@ -1231,6 +1358,36 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
     }
     tm.end(call_ti, OM_KT_BOUNCE_SPAN, st, launches);
     return hipSuccess;
+}
+
+// Workgroups the device holds at once at the bounce kernels' occupancy request (OM_WF_WAVES waves
+// per SIMD, 4 SIMDs per CU): the grid cap of the persistent k_query.
+uint32_t query_max_grid() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return (uint32_t)cus * (uint32_t)(OM_WF_WAVES * 4 * 64 / kBlk);
+}
+
+// One k_query launch on `st`: the variant renders would trace with (pick_trace), MARCH / USER
+// from the world's marched and SDF-program counts.
+hipError_t query(const Query& Q, hipStream_t st) {
+    if (Q.n == 0) return hipSuccess;
+    const int tr = pick_trace(Q.trace_mode, Q.S);
+    const uint32_t lds = trace_lds(tr, Q.S);
+    const bool march = (Q.S.n_msph + Q.S.n_mbox + Q.S.n_mtor + Q.S.n_msdf) != 0u;
+    const bool user = Q.S.n_msdf != 0u;
+    OmParamsDev P{};
+    P.tmin = Q.tmin; P.tmax = Q.tmax; P.march_steps = Q.march_steps;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)Q.n + kBlk - 1u) / kBlk, query_max_grid());
+    with_tr(tr, [&](auto t) {
+        constexpr int TR = decltype(t)::value;
+        if (user) launch_query<TR, true, true>(Q, P, grid, lds, st);
+        else if (march) launch_query<TR, true, false>(Q, P, grid, lds, st);
+        else launch_query<TR, false, false>(Q, P, grid, lds, st);
+    });
+    return hipGetLastError();
 }
 
 }  // namespace omw

@@ -451,6 +451,22 @@ om_status om_world_counts(const om_world* w, uint32_t counts[8]) {
     return OM_OK;
 }
 
+// HitRecord.material of an om_hit / om_pixel_stats obj id (global type-order index + 1)
+om_status om_world_object_material(const om_world* w, uint32_t obj, om_material* out) {
+    if (!w || !out) return fail(OM_ERR_INVALID, "om_world_object_material: null pointer");
+    if (obj == 0u) return fail(OM_ERR_INVALID, "om_world_object_material: obj 0 is no object");
+    size_t i = obj - 1u;
+    auto in = [&](const auto& v) {
+        if (i < v.size()) { *out = v[i].mat; return true; }
+        i -= v.size();
+        return false;
+    };
+    if (in(w->spheres) || in(w->cubes) || in(w->triangles) || in(w->planes) || in(w->parallelograms) || in(w->msph) ||
+        in(w->mbox) || in(w->mtor) || in(w->msdf))
+        return OM_OK;
+    return fail(OM_ERR_INVALID, "om_world_object_material: obj past the last object");
+}
+
 om_status om_world_export(const om_world* w, int32_t kind, uint32_t i, float* out, uint32_t n) {
     if (!w || !out) return fail(OM_ERR_INVALID, "om_world_export: null pointer");
     if (kind == K_SPHERE || kind == K_CUBE) {
