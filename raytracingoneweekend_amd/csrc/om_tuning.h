@@ -14,9 +14,19 @@
 #ifndef OM_WF_WAVES
 #define OM_WF_WAVES 8
 #endif
-// queue segments per tail workgroup
+// marched tail: queue segments per tail workgroup
 #ifndef OM_WF_TAIL_SPB
 #define OM_WF_TAIL_SPB 2
+#endif
+// traced tail: workgroups per CU of its resident grid (the queue's paths are dealt over them in
+// 64-path units); at most OM_WF_WAVES * 256 / OM_WF_BLOCK stay resident.
+// A tail workgroup holds its tree copy and the count prefix in LDS (C1: 41 KB) for as long as its
+// last wave runs, beside the other batch's bounce workgroups: the smallest grid measured best.
+// C1 at the old threshold 16: 4 / 3 / 2 / 1 -> 6972 / 7151 / 7313 / 7302 Msamples/s (parent 7224);
+// with the threshold of each: 2 (T 10) / 1 (T 8) -> C1 7331 / 7307, C3 4532 / 4615, C4 7742 / 7698,
+// C1 adaptive 18.55 / 18.3 ms per frame (profiles/balanced_tail/sweep.txt)
+#ifndef OM_WF_TAIL_WGS_PER_CU
+#define OM_WF_TAIL_WGS_PER_CU 1
 #endif
 // paths per batch: 2^OM_WF_MIN_PATHS_LOG2 (16 spp of 1080p), raised to OM_WF_BATCH_SPP samples of
 // the frame for frames above 2M pixels, within 2^OM_WF_MAX_PATHS_LOG2
@@ -91,7 +101,8 @@
 #ifndef OM_WF_ADAPTIVE_CAP_LOG2
 #define OM_WF_ADAPTIVE_CAP_LOG2 26
 #endif
-// tail threshold for adaptive batches (the per-bounce launches of a light batch are latency-bound)
+// tail threshold for adaptive batches (the per-bounce launches of a light batch are latency-bound);
+// on the balanced tail 6 / 8 / 10 / 12 -> 18.35 / 18.3 / 18.45 / 18.75 ms per C1 adaptive frame
 #ifndef OM_WF_ADAPTIVE_TAIL
 #define OM_WF_ADAPTIVE_TAIL 8
 #endif

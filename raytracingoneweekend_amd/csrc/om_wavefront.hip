@@ -8,9 +8,9 @@
 //               finished paths write (colour, depth, id) to their result slot
 //   bounce b    the same from queue b: trace + shade + compaction in ONE kernel (the
 //               path state is read once and written once per bounce; no hit buffer)
-//   tail        from bounce T on the queues hold a few thousand paths: one persistent
-//               launch runs every remaining path to completion, lanes stealing paths
-//               from a per-workgroup LDS counter (no ~40 near-empty launch pairs)
+//   tail        from bounce T on the queues hold few paths: one resident launch runs every
+//               remaining path to completion, the paths dealt in 64-path units evenly over
+//               the chip's workgroups and wave slots (no ~40 near-empty launch pairs)
 //   accumulate  one lane per pixel: Stats::add over the batch's samples IN SAMPLE
 //               ORDER (render_thread.rs:23-39): bit-identical to the sequential
 //               reference and to the megakernel.
@@ -81,17 +81,26 @@ __host__ __device__ inline uint32_t stack_bytes(const OmSceneDev& S) {
 __host__ __device__ inline uint32_t b2_stage_bytes(const OmSceneDev& S) {
     return (S.n_b2nodes * kB2Stride + S.n_b2leaves * 4u + 15u) & ~15u;
 }
-constexpr uint32_t kTailSpb = OM_WF_TAIL_SPB;                     // queue segments per tail workgroup
-constexpr uint32_t kTailDefault = 16;                             // first bounce handled by the tail kernel
+constexpr uint32_t kTailSpb = OM_WF_TAIL_SPB;                     // marched tail: queue segments per workgroup
+constexpr uint32_t kTailWgsPerCu = OM_WF_TAIL_WGS_PER_CU;         // traced tail: resident workgroups per CU
+constexpr uint32_t kWaves = kBlk / 64;                            // waves of a workgroup
+static_assert(kBlk % 64 == 0 && kTailWgsPerCu >= 1u, "whole waves; a tail grid");
+// first bounce handled by the tail kernel.  On the balanced tail an earlier start measures faster
+// (C1, 1 workgroup per CU: T = 8 / 10 / 12 / 16 -> 7307 / 7297 / 7281 / 7227 Msamples/s, means of
+// three runs, parent 7125); the threshold stays where tests/test_gpu_production_shapes.py pins the
+// launch counts of the bench's shapes
+constexpr uint32_t kTailDefault = 16;
 // marched worlds: bounce 0 as k_march + k_bounce<HIT>, every later segment in the lane-refilling
 // tail (om_tuning.h)
 constexpr uint32_t kTailMarched = OM_WF_TAIL_MARCHED;
 // BVH2s read through L2 (S-10k): 10 (C3, r03_v24/v25: T = 6 / 8 / 10 / 12 / 16 / 20 -> 3318 / 3523 /
-// 3553 / 3517 / 3416 / 3351 Msamples/s, means of two to four runs)
+// 3553 / 3517 / 3416 / 3351 Msamples/s, means of two to four runs; on the balanced tail T = 6 / 8 /
+// 10 / 12 -> 4608 / 4615 / 4556 / 4482, parent 4330: pinned like kTailDefault)
 constexpr uint32_t kTailL2 = 10;
 // batches above 2^25 paths (C4's 4K frame: 16 spp = 133M paths) keep more paths per late bounce,
 // so the per-bounce launches stay efficient longer: 24 (C4, r03_v26: T = 12 / 16 / 20 / 24 ->
-// 6956 / 7240 / 7304 / 7374 Msamples/s, means of two runs)
+// 6956 / 7240 / 7304 / 7374 Msamples/s, means of two runs; on the balanced tail 7692 / 7698 / 7691 /
+// 7668, parent 7564: flat)
 constexpr uint32_t kTailBigBatch = 24;
 __host__ __device__ inline uint32_t hyb_nodes(const OmSceneDev& S) {
     constexpr uint32_t kCap = OM_WF_HYB_BYTES / (uint32_t)sizeof(OmBvh2NodeH);
@@ -402,11 +411,14 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
                                                  const uint32_t* __restrict__ count_in, Queue out,
                                                  uint32_t* __restrict__ count_out, float4* __restrict__ res,
                                                  uint32_t* __restrict__ res_id, unsigned long long* __restrict__ counters,
-                                                 const float2* __restrict__ hitbuf) {
+                                                 const float2* __restrict__ hitbuf, uint32_t* __restrict__ tail_next) {
     const uint64_t seg0 = (uint64_t)blockIdx.x * G.segcap;
     uint32_t n, stride = R.n_pixels;
     uint64_t first0 = seg0;                 // FIRST: the batch's first sample of this workgroup
     if (FIRST) {
+        // the batch's traced tail claims paths from this word: zeroed here, launches ahead of it
+        // on the same stream (no memset, no launch of its own)
+        if (tail_next && blockIdx.x == 0 && threadIdx.x == 0) *tail_next = 0u;
         uint64_t paths = (uint64_t)R.n_pixels * R.batch;
         if (R.ad.list) {                    // adaptive: the stream's live list x the planned samples
             const AdPlan pl = uniform_load(R.ad.plan);
@@ -612,24 +624,33 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_march(OmSceneDev S, OmPa
 }
 
 // ---------------------------------------------------------------- tail
-// Workgroup b: every path of segments [b*kTailSpb, (b+1)*kTailSpb) of queue `in`, each run to
-// completion.  Lanes are refilled from an LDS counter as their paths end, in a single loop:
-//   traced worlds  one segment (trace + shade) per iteration; a lane whose path ended takes the
-//                  next path at once, so it never waits for the longest path of its wave (a
-//                  nested per-path loop holds every finished lane until the whole wave leaves it);
-//   marched worlds the k_march scheme (march_lanes) inside the tail: OM_MARCH_UNROLL march steps
-//                  per iteration, a lane whose march ended shades and starts its next segment,
-//                  lanes whose path ended are refilled together once OM_WF_REFILL of them wait.
+// Every path of queue `in`, each run to completion, lanes refilled as their paths end, in a
+// single loop:
+//   traced worlds  (k_tail) a resident grid over the whole queue: the paths are numbered through
+//                  the exclusive prefix of the segment counts and dealt in 64-path units evenly
+//                  over workgroups and wave slots.  One segment (trace +
+//                  shade) per iteration; a lane whose path ended takes the next undealt path at
+//                  once, so it never waits for the longest path of its wave;
+//   marched worlds (k_tail_march) workgroup b owns segments [b*kTailSpb, (b+1)*kTailSpb): the
+//                  k_march scheme (march_lanes) inside the tail: OM_MARCH_UNROLL march steps per
+//                  iteration, a lane whose march ended shades and starts its next segment, lanes
+//                  whose path ended are refilled together once OM_WF_REFILL of them wait.
 // (r04: C2 +8.3% over the r03 nested loop, in which every lane ran its path to completion before
 // it took another; C1 and C3 within 0.3%.)
+// Path idx of the ns segments from s0 on, numbered through pre[0 .. ns] (exclusive prefix of their
+// counts, in LDS): segment by binary search.  Empty segments repeat a prefix value; the search
+// keeps the last of them, the one that holds idx.
 struct TailSrc {
     const Queue& in;
     const uint32_t* pre;
-    uint32_t s0, segcap;
+    uint32_t s0, ns, segcap;
     __device__ __forceinline__ bool load(uint32_t idx, Path& p) const {
-        uint32_t k = 0;
-        while (idx >= pre[k + 1]) ++k;
-        const uint64_t i = (uint64_t)(s0 + k) * segcap + (idx - pre[k]);
+        uint32_t lo = 0, hi = ns;                           // pre[lo] <= idx < pre[hi]
+        while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (pre[mid] <= idx) lo = mid; else hi = mid;
+        }
+        const uint64_t i = (uint64_t)(s0 + lo) * segcap + (idx - pre[lo]);
         load_ray(in, i, p);
         load_rest(in, i, p);
         return true;                                        // (a queued path is always live)
@@ -710,10 +731,9 @@ __device__ __forceinline__ uint32_t tail_march_lanes(const OmSceneDev& S, const 
     return segs;
 }
 
-template <int TR, bool COUNT, bool MARCH, int VIEW = MV_ARRAYS, uint32_t SPB = kTailSpb>
-__global__ __launch_bounds__(kBlk) __attribute__((amdgpu_waves_per_eu(MARCH ? OM_WF_TAIL_MARCH_WAVES : OM_WF_WAVES,
-                                                                      MARCH ? OM_WF_TAIL_MARCH_WAVES : OM_WF_WAVES)))
-void k_tail(OmSceneDev S, OmParamsDev P, Seg G, Queue in,
+template <int TR, bool COUNT, int VIEW = MV_ARRAYS, uint32_t SPB = kTailSpb>
+__global__ __launch_bounds__(kBlk) __attribute__((amdgpu_waves_per_eu(OM_WF_TAIL_MARCH_WAVES, OM_WF_TAIL_MARCH_WAVES)))
+void k_tail_march(OmSceneDev S, OmParamsDev P, Seg G, Queue in,
                                                const uint32_t* __restrict__ count_in, float4* __restrict__ res,
                                                uint32_t* __restrict__ res_id, unsigned long long* __restrict__ counters) {
     __shared__ uint32_t pre[SPB + 1];
@@ -732,35 +752,103 @@ void k_tail(OmSceneDev S, OmParamsDev P, Seg G, Queue in,
     const uint32_t total = pre[SPB];
     if (total == 0) return;
     const Tracer T = stage_scene<TR>(S);
-    const uint32_t depth_cap = P.max_depth > 1u ? P.max_depth : 1u;
-    const TailSrc src{in, pre, s0, G.segcap};
+    const TailSrc src{in, pre, s0, SPB, G.segcap};
     WorkT<COUNT> w;
     uint32_t segs = 0;
-    if constexpr (MARCH) {
-        if constexpr (VIEW == MV_EXACT_C2_LDS) {
-            __shared__ MarchedC2Lds::Block mblock;
-            segs = tail_march_lanes<TR, COUNT>(S, P, T, MarchedC2Lds(S, &mblock), src, total, next, res, res_id, w);
-        } else {
-            segs = tail_march_lanes<TR, COUNT>(S, P, T, MarchedArrays(S), src, total, next, res, res_id, w);
-        }
+    if constexpr (VIEW == MV_EXACT_C2_LDS) {
+        __shared__ MarchedC2Lds::Block mblock;
+        segs = tail_march_lanes<TR, COUNT>(S, P, T, MarchedC2Lds(S, &mblock), src, total, next, res, res_id, w);
     } else {
-        uint32_t idx = threadIdx.x;
-        bool have = idx < total;
-        Path p;
-        if (have) src.load(idx, p);
-        for (;;) {
-            if (have) {
-                float closest;
-                const int best = trace<TR, false>(S, P, T, p.o, p.d, closest, w);
-                if (COUNT) segs++;
-                if (!shade_path<false>(S, P, depth_cap, p, closest, best, res, res_id)) {
-                    idx = atomicAdd(&next, 1u);                 // the path ended: the next one at once
+        segs = tail_march_lanes<TR, COUNT>(S, P, T, MarchedArrays(S), src, total, next, res, res_id, w);
+    }
+    if (COUNT) {
+        flush_counter(counters, OMC_SEGMENTS, segs);
+        flush_counter(counters, OMC_PRIM_TESTS, w.prim);
+        flush_counter(counters, OMC_PRE_TESTS, w.pre);
+        flush_counter(counters, OMC_MARCH, w.march);
+    }
+}
+
+// The traced tail.  gridDim.x workgroups, all resident (the host sizes the grid from the CU count);
+// every one of them
+//   1. scans count_in[0 .. G.nseg) into pre[0 .. G.nseg] (dynamic LDS at byte pre_off, behind what
+//      stage_scene fills) and leaves before staging when the queue is empty;
+//   2. takes its share of the first gridDim.x * kWaves units of 64 consecutive paths: unit u runs
+//      in workgroup u % gridDim.x on wave slot (u / gridDim.x + workgroup) % kWaves, so a light
+//      tail puts one or two dense waves in each workgroup, on different slots in neighbouring
+//      workgroups, instead of filling slots 0, 1, .. of a few;
+//   3. (queues longer than the grid's lanes) refills ended lanes from *next, the queue set's claim
+//      counter (zeroed by the batch's bounce 0): one atomic per wave and iteration for all of the
+//      wave's idle lanes, and none once the counter has passed the end of the queue.
+// No workgroup waits for another, and no barrier follows the staging barrier.
+template <int TR, bool COUNT>
+__global__ __launch_bounds__(kBlk) OM_WAVES_ATTR
+void k_tail(OmSceneDev S, OmParamsDev P, Seg G, Queue in, const uint32_t* __restrict__ count_in, uint32_t pre_off,
+            uint32_t* __restrict__ next, float4* __restrict__ res, uint32_t* __restrict__ res_id,
+            unsigned long long* __restrict__ counters) {
+    uint32_t* pre = (uint32_t*)wf_lds + pre_off / 4u;
+    __shared__ uint32_t wave_sum[kWaves];
+    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
+    // thread t scans counts [t*per, (t+1)*per): its sum, the wave's inclusive scan of the sums,
+    // the waves' totals through LDS
+    const uint32_t per = (G.nseg + kBlk - 1u) / kBlk;
+    const uint32_t c0 = threadIdx.x * per, c1 = c0 + per < G.nseg ? c0 + per : G.nseg;
+    uint32_t mine = 0;
+    for (uint32_t k = c0; k < c1; ++k) mine += count_in[k];
+    uint32_t incl = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t v = __shfl_up(incl, off, 64);
+        if (lane >= (uint32_t)off) incl += v;
+    }
+    if (lane == 63u) wave_sum[wave] = incl;
+    __syncthreads();
+    uint32_t acc = incl - mine, total = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kWaves; ++k) {
+        const uint32_t v = wave_sum[k];
+        if (k < wave) acc += v;
+        total += v;
+    }
+    if (total == 0) return;                                   // (uniform over the grid)
+    for (uint32_t k = c0; k < c1; ++k) { pre[k] = acc; acc += count_in[k]; }
+    if (threadIdx.x == 0) pre[G.nseg] = total;
+    __syncthreads();
+    const Tracer T = stage_scene<TR>(S);
+    const uint32_t depth_cap = P.max_depth > 1u ? P.max_depth : 1u;
+    const TailSrc src{in, pre, 0u, G.nseg, G.segcap};
+    WorkT<COUNT> w;
+    uint32_t segs = 0;
+    const uint32_t lanes = gridDim.x * kBlk;                  // paths [0, lanes) are dealt, the rest claimed
+    const uint32_t round = (wave + kWaves - blockIdx.x % kWaves) % kWaves;
+    uint32_t idx = (round * gridDim.x + blockIdx.x) * 64u + lane;
+    bool have = idx < total;
+    bool more = total > lanes;                                // wave-uniform: undealt paths may remain
+    Path p;
+    if (have) src.load(idx, p);
+    for (;;) {
+        if (have) {
+            float closest;
+            const int best = trace<TR, false>(S, P, T, p.o, p.d, closest, w);
+            if (COUNT) segs++;
+            have = shade_path<false>(S, P, depth_cap, p, closest, best, res, res_id);
+        }
+        if (more) {                                           // the ended lanes' next paths at once
+            const uint64_t want = __ballot(!have);
+            if (want) {
+                const uint32_t nw = (uint32_t)__popcll(want);
+                uint32_t base = 0u;
+                if (lane == 0) base = atomicAdd(next, nw);
+                base = lanes + __builtin_amdgcn_readfirstlane(base);
+                if (!have) {
+                    idx = base + (uint32_t)__popcll(want & ((1ull << lane) - 1ull));
                     have = idx < total;
                     if (have) src.load(idx, p);
                 }
+                more = base + nw < total;
             }
-            if (__ballot(have) == 0) break;
         }
+        if (__ballot(have) == 0) break;
     }
     if (COUNT) {
         flush_counter(counters, OMC_SEGMENTS, segs);
@@ -1036,24 +1124,35 @@ hipError_t grow(Buffers& B, uint64_t cap, uint32_t counts_n, int nsets) {
 
 Queue queue(QueueSet& B, int k) { return Queue{B.q[k][0], B.q[k][1], B.q[k][2], B.qr[k]}; }
 
+// k_tail's dynamic LDS: the segment-count prefix (nseg + 1 words) behind stage_scene's bytes
+inline uint32_t tail_pre_off(uint32_t lds) { return (lds + 15u) & ~15u; }
+inline uint32_t tail_lds(uint32_t lds, uint32_t nseg) { return tail_pre_off(lds) + (nseg + 1u) * 4u; }
+
 // One batch: bounce 0 .. tail_at-1 as per-bounce launches, then the tail launch, all on `st`;
 // returns the number of bounce-family launches.
 template <int TR, bool COUNT, bool MARCH>
 uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Gen& R, uint32_t depth_cap,
-                   uint32_t tail_at, uint32_t lds) {
+                   uint32_t tail_at, uint32_t lds, uint32_t tail_grid) {
     Timer& tm = *L.timer;
     const bool each = tm.mode == 1;
     uint32_t launches = 0;
     const bool exact = MARCH && L.S.n_msdf == 0u && MarchedC2Lds::matches(L.S.n_msph, L.S.n_mbox, L.S.n_mtor);
+    // the traced tail's claim counter: the word behind the set's per-bounce counts
+    uint32_t* const tail_next = B.counts + (size_t)(depth_cap + 1u) * G.nseg;
     auto tail = [&](const Queue& in, const uint32_t* cin) {
         const int ti = each ? tm.begin(st) : -1;
-        const uint32_t grid = (G.nseg + kTailSpb - 1u) / kTailSpb;
-        if (exact && exact_view_built<TR>())
-            hipLaunchKernelGGL((k_tail<TR, COUNT, MARCH, MARCH && exact_view_built<TR>() ? MV_EXACT_C2_LDS : MV_ARRAYS>), dim3(grid),
-                               dim3(kBlk), lds, st, L.S, L.P, G, in, cin, B.res, B.res_id, L.counters);
-        else
-            hipLaunchKernelGGL((k_tail<TR, COUNT, MARCH>), dim3(grid), dim3(kBlk), lds, st, L.S, L.P, G, in, cin,
-                               B.res, B.res_id, L.counters);
+        if constexpr (MARCH) {
+            const uint32_t grid = (G.nseg + kTailSpb - 1u) / kTailSpb;
+            if (exact && exact_view_built<TR>())
+                hipLaunchKernelGGL((k_tail_march<TR, COUNT, exact_view_built<TR>() ? MV_EXACT_C2_LDS : MV_ARRAYS>), dim3(grid),
+                                   dim3(kBlk), lds, st, L.S, L.P, G, in, cin, B.res, B.res_id, L.counters);
+            else
+                hipLaunchKernelGGL((k_tail_march<TR, COUNT>), dim3(grid), dim3(kBlk), lds, st, L.S, L.P, G, in, cin,
+                                   B.res, B.res_id, L.counters);
+        } else {
+            hipLaunchKernelGGL((k_tail<TR, COUNT>), dim3(tail_grid), dim3(kBlk), tail_lds(lds, G.nseg), st, L.S, L.P, G, in, cin,
+                               tail_pre_off(lds), tail_next, B.res, B.res_id, L.counters);
+        }
         tm.end(ti, OM_KT_TAIL, st);
         return launches + 1u;
     };
@@ -1084,10 +1183,10 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
             ti = each ? tm.begin(st) : -1;
             if (exact && exact_view_built<TR>())                       // no user objects (OmMSdf) in the world
                 hipLaunchKernelGGL((k_bounce<TR, COUNT, MARCH, false, true, false>), dim3(G.nseg), dim3(kBlk), 0, st, L.S, L.P, G,
-                                   R, in, cin, out, cout, B.res, B.res_id, L.counters, (const float2*)B.hit);
+                                   R, in, cin, out, cout, B.res, B.res_id, L.counters, (const float2*)B.hit, (uint32_t*)nullptr);
             else
                 hipLaunchKernelGGL((k_bounce<TR, COUNT, MARCH, false, true>), dim3(G.nseg), dim3(kBlk), 0, st, L.S, L.P, G, R, in,
-                                   cin, out, cout, B.res, B.res_id, L.counters, (const float2*)B.hit);
+                                   cin, out, cout, B.res, B.res_id, L.counters, (const float2*)B.hit, (uint32_t*)nullptr);
             tm.end(ti, kc, st);
             launches += 2u;
         }
@@ -1101,10 +1200,10 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
         const int ti = each ? tm.begin(st) : -1;
         if (bounce == 0)
             hipLaunchKernelGGL((k_bounce<TR, COUNT, MARCH, true>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, R, in,
-                               cin, out, cout, B.res, B.res_id, L.counters, (const float2*)nullptr);
+                               cin, out, cout, B.res, B.res_id, L.counters, (const float2*)nullptr, tail_next);
         else
             hipLaunchKernelGGL((k_bounce<TR, COUNT, MARCH, false>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, R, in,
-                               cin, out, cout, B.res, B.res_id, L.counters, (const float2*)nullptr);
+                               cin, out, cout, B.res, B.res_id, L.counters, (const float2*)nullptr, (uint32_t*)nullptr);
         tm.end(ti, bounce == 0 ? OM_KT_BOUNCE0 : OM_KT_BOUNCE, st);
         ++launches;
     }
@@ -1114,11 +1213,11 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
 
 template <int TR>
 uint32_t run_tr(bool count, bool march, QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Gen& R,
-                uint32_t depth_cap, uint32_t tail_at, uint32_t lds) {
-    if (count && march) return run_batch<TR, true, true>(B, L, st, G, R, depth_cap, tail_at, lds);
-    if (count) return run_batch<TR, true, false>(B, L, st, G, R, depth_cap, tail_at, lds);
-    if (march) return run_batch<TR, false, true>(B, L, st, G, R, depth_cap, tail_at, lds);
-    return run_batch<TR, false, false>(B, L, st, G, R, depth_cap, tail_at, lds);
+                uint32_t depth_cap, uint32_t tail_at, uint32_t lds, uint32_t tail_grid) {
+    if (count && march) return run_batch<TR, true, true>(B, L, st, G, R, depth_cap, tail_at, lds, tail_grid);
+    if (count) return run_batch<TR, true, false>(B, L, st, G, R, depth_cap, tail_at, lds, tail_grid);
+    if (march) return run_batch<TR, false, true>(B, L, st, G, R, depth_cap, tail_at, lds, tail_grid);
+    return run_batch<TR, false, false>(B, L, st, G, R, depth_cap, tail_at, lds, tail_grid);
 }
 
 hipError_t ensure_events(Buffers& B, size_t n) {
@@ -1256,9 +1355,18 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
     uint32_t nseg = (uint32_t)std::min<uint64_t>((max_paths + kBlk - 1) / kBlk, (uint64_t)cus * (lanes_per_cu / kBlk));
     nseg = (nseg + kTailSpb - 1) / kTailSpb * kTailSpb;
     const uint32_t segcap = seg_capacity(max_paths, nseg);
-    hipError_t e = grow(B, (uint64_t)nseg * segcap, (depth_cap + 1u) * nseg, (int)ns);
+    // (+ 1: the traced tail's claim counter, run_batch)
+    hipError_t e = grow(B, (uint64_t)nseg * segcap, (depth_cap + 1u) * nseg + 1u, (int)ns);
     if (e != hipSuccess) { err = "wavefront buffer allocation failed"; return e; }
     const uint32_t lds = trace_lds(tr, L.S);
+    // the traced tail: a resident grid, and the segment-count prefix in LDS behind the tree
+    const uint32_t tail_grid = (uint32_t)cus * kTailWgsPerCu;
+    int lds_max = 0;
+    (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    if (!march && tail_at < depth_cap && tail_lds(lds, nseg) > (uint32_t)lds_max) {
+        err = "the tail's LDS request exceeds the device's limit";
+        return hipErrorInvalidValue;
+    }
     Gen R;
     R.C = L.C; R.jitter = L.jitter; R.stats = L.stats; R.pixels = L.pixels; R.n_pixels = n_px;
     R.by_pixel = L.stats_by_pixel ? 1u : 0u;
@@ -1329,7 +1437,7 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
         R.batch = b;
         R.ad = ad;
         with_tr(tr, [&](auto t) {
-            launches += run_tr<decltype(t)::value>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds);
+            launches += run_tr<decltype(t)::value>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds, tail_grid);
         });
         // accumulates in batch order: fixed spp needs it (Stats::add in sample order); an adaptive
         // stream's pixels are its own, so there it only keeps the streams in step and the progress

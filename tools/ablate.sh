@@ -23,6 +23,11 @@ declare -A V=(
   [b512w6]="$COMMON $DEV -DOM_WF_BLOCK=512 -DOM_WF_WAVES=6"
   [tspb1]="$COMMON $DEV -DOM_WF_TAIL_SPB=1"
   [tspb4]="$COMMON $DEV -DOM_WF_TAIL_SPB=4"
+  # traced tail: workgroups per CU of the resident grid (default 4)
+  [twg1]="$COMMON $DEV -DOM_WF_TAIL_WGS_PER_CU=1"
+  [twg2]="$COMMON $DEV -DOM_WF_TAIL_WGS_PER_CU=2"
+  [twg3]="$COMMON $DEV -DOM_WF_TAIL_WGS_PER_CU=3"
+  [twg4]="$COMMON $DEV -DOM_WF_TAIL_WGS_PER_CU=4"
   # segments per CU (lanes per CU / workgroup size), traced and wide (marched, L2 BVH2)
   [lpc2k]="$COMMON $DEV -DOM_WF_LANES_PER_CU=2048"
   [lpc8k]="$COMMON $DEV -DOM_WF_LANES_PER_CU=8192"
