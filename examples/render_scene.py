@@ -6,6 +6,7 @@ the F12 save of main.rs:473-476.
 
     python examples/render_scene.py --width 1000 --height 666 --spp 200 --out out/
     python examples/render_scene.py --width 1000 --height 666 --pick 500 400      # what is under a pixel
+    python examples/render_scene.py --width 1000 --height 666 --ao 16 0.5         # ambient occlusion, out/ao.bmp
 """
 import argparse
 import os
@@ -37,6 +38,43 @@ def pick(world, frozen, cam, W, H, x, y):
     print(f"pixel ({x}, {y}): obj {h.obj}, t {h.t:.6g}, point {tuple(float(c) for c in h.point)}, {world.material_of(h.obj)}")
 
 
+def pinhole_rays(cam, W, H):
+    """(W*H, 6) float32 centre rays of the frame, row-major, from a pinhole at the camera origin."""
+    F = np.float32
+    r = cam.raw
+    org, hor, ver, llc = (np.array(list(v), dtype=F) for v in (r.origin, r.horizontal, r.vertical, r.lower_left_corner))
+    j, i = np.meshgrid(np.arange(H, dtype=F), np.arange(W, dtype=F), indexing="ij")
+    u = ((i.reshape(-1) + F(0.5)) / F(W)).astype(F)
+    v = (F(1.0) - (j.reshape(-1) + F(0.5)) / F(H)).astype(F)
+    d = (llc[None, :] + u[:, None] * hor[None, :] + v[:, None] * ver[None, :] - org[None, :]).astype(F)
+    d = (d / np.sqrt((d * d).sum(axis=1, dtype=F), dtype=F)[:, None]).astype(F)
+    return np.ascontiguousarray(np.concatenate([np.broadcast_to(org, d.shape), d], axis=1), dtype=F)
+
+
+def ambient_occlusion(frozen, cam, W, H, samples, radius, seed):
+    """Grey (H, W, 3) u8 image: per pixel, the share of `samples` seeded hemisphere rays of length
+    `radius` from its primary hit point that reach nothing (sky pixels stay white).  Primary hits
+    through hit_rays; the AO rays through occluded() with the per-ray window [0.001, radius]."""
+    F = np.float32
+    hits = frozen.hit_rays(pinhole_rays(cam, W, H))
+    on = np.nonzero(hits["obj"])[0]
+    n = hits["normal"][on]
+    n = (n / np.sqrt((n * n).sum(axis=1, dtype=F), dtype=F)[:, None]).astype(F)      # cube normals are not unit
+    rng = np.random.default_rng(seed)
+    win = np.zeros(len(on), dtype=om.WINDOW_DTYPE)
+    win["tmin"], win["tmax"] = F(0.001), F(radius)
+    open_count = np.zeros(len(on), dtype=np.uint32)
+    for _ in range(samples):
+        d = rng.standard_normal((len(on), 3)).astype(F)
+        d = (d / np.sqrt((d * d).sum(axis=1, dtype=F), dtype=F)[:, None]).astype(F)
+        d = np.where((d * n).sum(axis=1, dtype=F)[:, None] < 0, -d, d).astype(F)
+        rays = np.ascontiguousarray(np.concatenate([hits["point"][on], d], axis=1), dtype=F)
+        open_count += ~frozen.occluded(rays, windows=win)
+    grey = np.full(W * H, 255, dtype=np.uint8)
+    grey[on] = np.round(255.0 * open_count / max(1, samples)).astype(np.uint8)
+    return np.ascontiguousarray(np.repeat(grey.reshape(H, W, 1), 3, axis=2))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1000)           # main.rs:125-127
@@ -53,6 +91,9 @@ def main():
     ap.add_argument("--ppm", action="store_true", help="write PPM instead of BMP")
     ap.add_argument("--pick", type=int, nargs=2, metavar=("X", "Y"),
                     help="print the object id, t and material under the centre of pixel (X, Y) and exit (no render)")
+    ap.add_argument("--ao", nargs=2, metavar=("SAMPLES", "RADIUS"),
+                    help="write ao.bmp/ppm: ambient occlusion from SAMPLES any-hit rays of length RADIUS per primary hit "
+                         "(FrozenHittableList.occluded), and exit (no render)")
     args = ap.parse_args()
 
     W, H = args.width, args.height
@@ -63,6 +104,18 @@ def main():
         if not (0 <= args.pick[0] < W and 0 <= args.pick[1] < H):
             ap.error("--pick: the pixel is outside the frame")
         pick(world, frozen, cam, W, H, *args.pick)
+        return
+    if args.ao:
+        samples, radius = int(args.ao[0]), float(args.ao[1])
+        if samples < 1 or not radius > 0.001:
+            ap.error("--ao: need SAMPLES >= 1 and RADIUS > 0.001")
+        t0 = time.perf_counter()
+        rgb = ambient_occlusion(frozen, cam, W, H, samples, radius, args.seed)
+        print(f"{W}x{H} ambient occlusion, {samples} rays of length {radius} per hit point, in {time.perf_counter() - t0:.3f} s")
+        os.makedirs(args.out, exist_ok=True)
+        path = os.path.join(args.out, f"ao.{'ppm' if args.ppm else 'bmp'}")
+        (om.write_ppm if args.ppm else om.write_bmp)(path, rgb)
+        print("wrote", path)
         return
     pixels = om.PixelsBox.new(W * H)
     t0, credited = time.perf_counter(), 0

@@ -264,6 +264,37 @@ om_status om_hit_rays_device(om_ctx* ctx, const om_query_params* q, const om_ray
 /* Host form, synchronous: copies through staging buffers the ctx owns (grown on demand, reused);
  * the copies run at DMA speed when the caller's buffers are page-locked (om_host_register). */
 om_status om_hit_rays(om_ctx* ctx, const om_query_params* q, const om_ray* rays, uint32_t n, om_hit* hits);
+/* ---- any-hit (occlusion) queries and per-ray windows ----
+ *   occluded(ray, tmin, tmax) := FrozenHittableList::hit(ray, tmin, tmax).is_some()
+ * for shadow, visibility and ambient-occlusion rays: the traversal stops at the first primitive
+ * whose own exact test accepts, the march runs only for rays no traced primitive answered, no
+ * HitRecord is built and one byte per ray is written.  The answer is the reference's, bit for bit.
+ *   om_ray_window  one [tmin, tmax] per ray.  `windows` NULL: q's tmin / tmax for every ray.
+ *            Per-ray windows are not validated: each ray gets what the reference gives for its
+ *            window, NaN and negative bounds included (the traced tests accept root == tmax and a
+ *            NaN tmax, the march does neither).  Rays whose window has tmin < 0 or a NaN bound run
+ *            the reference loop itself, like rays with non-finite components.
+ *   occluded[i]    written for every i < n as exactly 0 or 1; no byte outside [0, n) is touched,
+ *            whatever the pointer's alignment.
+ * q is validated as for om_hit_rays* whether or not windows are given (its march_steps always
+ * applies), and status codes, counters, the unit-direction precondition and the one-stream-per-ctx
+ * rule are those of om_hit_rays*: n == 0 is OM_OK and launches nothing; a null ctx, q, rays or
+ * output with n > 0, reserved != 0 or a NaN q->tmin / q->tmax is OM_ERR_INVALID; a call before
+ * om_upload_world is OM_ERR_STATE; a failed call writes nothing.  With counting on, a call adds n
+ * to om_counters.segments and the exact tests, pre-tests and march steps it really ran; samples,
+ * credited and the om_progress word are untouched. */
+typedef struct om_ray_window { float tmin, tmax; } om_ray_window;              /* 8 B */
+om_status om_occluded_rays_device(om_ctx* ctx, const om_query_params* q, const om_ray* dev_rays,
+                                  const om_ray_window* dev_windows /* NULL: q's tmin/tmax for every ray */,
+                                  uint32_t n, uint8_t* dev_occluded, void* stream);
+om_status om_occluded_rays(om_ctx* ctx, const om_query_params* q, const om_ray* rays,
+                           const om_ray_window* windows, uint32_t n, uint8_t* occluded);
+/* Closest hit of ray i in [dev_windows[i].tmin, dev_windows[i].tmax]: om_hit_rays* with one window
+ * per ray (NULL: q's window, exactly om_hit_rays*). */
+om_status om_hit_rays_windows_device(om_ctx* ctx, const om_query_params* q, const om_ray* dev_rays,
+                                     const om_ray_window* dev_windows, uint32_t n, om_hit* dev_hits, void* stream);
+om_status om_hit_rays_windows(om_ctx* ctx, const om_query_params* q, const om_ray* rays,
+                              const om_ray_window* windows, uint32_t n, om_hit* hits);
 /* Workgroups of the largest query launch on ctx's device (the kernel is persistent: a workgroup
  * stages the tree once and loops over blocks of OM_QUERY_BLOCK rays); 0 on error. */
 #define OM_QUERY_BLOCK 512

@@ -328,6 +328,37 @@ public:
         check(om_hit_rays(ctx_, &q, rays.data(), (uint32_t)rays.size(), hits.data()), ctx_);
         return hits;
     }
+    // hit_rays with one [tmin, tmax] per ray (om_hit_rays_windows); t_min / t_max are validated
+    // but every ray is answered for its own window.
+    std::vector<om_hit> hit_rays(const std::vector<om_ray>& rays, float t_min, float t_max, const std::vector<om_ray_window>& windows,
+                                 uint32_t march_steps = 1024) const {
+        if (windows.size() != rays.size()) throw Error(OM_ERR_INVALID, "hit_rays: one window per ray");
+        std::vector<om_hit> hits(rays.size());
+        const om_query_params q{t_min, t_max, march_steps, 0u};
+        check(om_hit_rays_windows(ctx_, &q, rays.data(), windows.data(), (uint32_t)rays.size(), hits.data()), ctx_);
+        return hits;
+    }
+    // Any-hit: hit(ray, t_min, t_max).is_some() (hits.rs:270-334) without the HitRecord, for shadow
+    // and ambient-occlusion rays (om_occluded_rays): the traversal stops at the first accepted primitive.
+    bool occluded(const Vec3& orig, const Vec3& dir, float t_min, float t_max, uint32_t march_steps = 1024) const {
+        om_ray r;
+        for (int k = 0; k < 3; ++k) { r.orig[k] = orig.e[k]; r.dir[k] = dir.e[k]; }
+        const om_query_params q{t_min, t_max, march_steps, 0u};
+        uint8_t occ = 0;
+        check(om_occluded_rays(ctx_, &q, &r, nullptr, 1u, &occ), ctx_);
+        return occ != 0;
+    }
+    // The same for a batch: one byte (0 / 1) per ray, in order; `windows` (empty: [t_min, t_max]
+    // for every ray) gives each ray its own window.
+    std::vector<uint8_t> occluded_rays(const std::vector<om_ray>& rays, float t_min, float t_max,
+                                       const std::vector<om_ray_window>& windows = {}, uint32_t march_steps = 1024) const {
+        if (!windows.empty() && windows.size() != rays.size()) throw Error(OM_ERR_INVALID, "occluded_rays: one window per ray");
+        std::vector<uint8_t> occ(rays.size());
+        const om_query_params q{t_min, t_max, march_steps, 0u};
+        check(om_occluded_rays(ctx_, &q, rays.data(), windows.empty() ? nullptr : windows.data(), (uint32_t)rays.size(), occ.data()),
+              ctx_);
+        return occ;
+    }
 
 private:
     om_ctx* ctx_ = nullptr;

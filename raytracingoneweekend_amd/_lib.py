@@ -58,10 +58,15 @@ class om_query_params(C.Structure):
     _fields_ = [("tmin", C.c_float), ("tmax", C.c_float), ("march_steps", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-# numpy views of om_ray / om_hit
+class om_ray_window(C.Structure):              # one [tmin, tmax] per ray, 8 B
+    _fields_ = [("tmin", C.c_float), ("tmax", C.c_float)]
+
+
+# numpy views of om_ray / om_hit / om_ray_window
+WINDOW_DTYPE = np.dtype([("tmin", "<f4"), ("tmax", "<f4")])
 RAY_DTYPE = np.dtype([("orig", "<f4", (3,)), ("dir", "<f4", (3,))])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("point", "<f4", (3,)), ("normal", "<f4", (3,)), ("obj", "<u4")])
-assert RAY_DTYPE.itemsize == 24 and HIT_DTYPE.itemsize == 32
+assert RAY_DTYPE.itemsize == 24 and HIT_DTYPE.itemsize == 32 and WINDOW_DTYPE.itemsize == 8
 OM_QUERY_BLOCK = 512
 
 
@@ -113,6 +118,7 @@ EXPORTS = [
     "om_multi_last_error", "om_progress", "om_reset_progress", "om_host_register", "om_host_unregister",
     "om_multi_render_host", "om_multi_gather", "om_multi_reset", "om_rccl_library",
     "om_hit_rays_device", "om_hit_rays", "om_world_object_material", "om_query_max_grid",
+    "om_occluded_rays_device", "om_occluded_rays", "om_hit_rays_windows_device", "om_hit_rays_windows",
 ]
 OM_COMM_ID_BYTES = 128
 OM_TRANSPORT_RCCL, OM_TRANSPORT_LOCAL = 0, 1
@@ -231,6 +237,10 @@ def _load():
         "om_hit_rays": (st, [vp, C.POINTER(om_query_params), vp, C.c_uint32, vp]),
         "om_world_object_material": (st, [vp, C.c_uint32, mp]),
         "om_query_max_grid": (C.c_uint32, [vp]),
+        "om_occluded_rays_device": (st, [vp, C.POINTER(om_query_params), vp, vp, C.c_uint32, vp, vp]),
+        "om_occluded_rays": (st, [vp, C.POINTER(om_query_params), vp, vp, C.c_uint32, vp]),
+        "om_hit_rays_windows_device": (st, [vp, C.POINTER(om_query_params), vp, vp, C.c_uint32, vp, vp]),
+        "om_hit_rays_windows": (st, [vp, C.POINTER(om_query_params), vp, vp, C.c_uint32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -24,11 +24,12 @@ from ._lib import check, f3, fptr, lib
 __all__ = [
     "Material", "Mat4x4", "m4x4", "Camera", "Sphere", "Cube", "Triangle", "Parallelogram", "InfinitePlane",
     "MarchedSphere", "MarchedBox", "MarchedTorus", "MarchedSdf", "HittableList", "FrozenHittableList", "PixelsBox", "render",
-    "RenderStats", "HitRecord", "HIT_DTYPE", "RAY_DTYPE",
+    "RenderStats", "HitRecord", "HIT_DTYPE", "RAY_DTYPE", "WINDOW_DTYPE",
 ]
 
 HIT_DTYPE = L.HIT_DTYPE     # om_hit: t, point, normal, obj (hits.rs:11-17)
 RAY_DTYPE = L.RAY_DTYPE     # om_ray: orig, dir (ray.rs:5-8)
+WINDOW_DTYPE = L.WINDOW_DTYPE   # om_ray_window: tmin, tmax of one ray
 
 
 # ---------------------------------------------------------------- materials.rs
@@ -363,7 +364,7 @@ class FrozenHittableList:
             return None
         return HitRecord(float(h["t"]), h["point"].copy(), h["normal"].copy(), int(h["obj"]))
 
-    def hit_rays(self, rays, tmin=0.001, tmax=100.0, march_steps=1024, out=None, stream=None):
+    def hit_rays(self, rays, tmin=0.001, tmax=100.0, march_steps=1024, out=None, stream=None, windows=None):
         """Closest hits of a batch of rays (om_hit_rays / om_hit_rays_device).
 
         `rays`: an (n, 6) float32 array (orig, dir per row; or an n-vector of RAY_DTYPE) -> an
@@ -375,23 +376,46 @@ class FrozenHittableList:
         (the ops that made `rays`) and before what is queued afterwards (the readers of the result).
         When torch's current stream is the null stream, whose handle the C entry point would read as
         "the ctx's own stream", the launch goes to a side stream of this object that is ordered
-        with the null stream by events on both sides."""
+        with the null stream by events on both sides.
+
+        `windows`: one [tmin, tmax] per ray instead of the call's (om_hit_rays_windows*): an (n, 2)
+        float32 array or an n-vector of WINDOW_DTYPE; with torch rays, an (n, 2) float32 tensor on
+        the rays' device.  Windows are not validated: every ray gets the reference's answer for
+        its own window, NaN and negative bounds included."""
+        return self._query("hit_rays", rays, tmin, tmax, march_steps, windows, out, stream)
+
+    def occluded(self, rays, tmin=0.001, tmax=100.0, march_steps=1024, windows=None, out=None, stream=None):
+        """Any-hit query: hit(ray, tmin, tmax).is_some() per ray (om_occluded_rays /
+        om_occluded_rays_device), for shadow, visibility and ambient-occlusion rays.
+
+        `rays` and `windows` as for hit_rays.  numpy in -> a numpy bool n-vector, synchronous; a
+        torch ROCm tensor in -> a torch.uint8 n-vector (0 / 1) on the same device, asynchronous,
+        with the stream rules of hit_rays."""
+        return self._query("occluded", rays, tmin, tmax, march_steps, windows, out, stream)
+
+    def _query(self, what, rays, tmin, tmax, march_steps, windows, out, stream):
+        occ = what == "occluded"
         q = L.om_query_params(float(tmin), float(tmax), int(march_steps), 0)
         if type(rays).__module__.split(".")[0] == "torch":
             import torch
             if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6 \
                     or not rays.is_contiguous():
-                raise ValueError("hit_rays: need a contiguous (n, 6) float32 tensor on the device")
+                raise ValueError(f"{what}: need a contiguous (n, 6) float32 tensor on the device")
             if rays.device.index != int(self.device):
-                raise ValueError(f"hit_rays: rays are on {rays.device}, the world is on device {self.device}")
+                raise ValueError(f"{what}: rays are on {rays.device}, the world is on device {self.device}")
             n = rays.shape[0]
+            if windows is not None:
+                if type(windows).__module__.split(".")[0] != "torch" or not windows.is_cuda or windows.dtype != torch.float32 \
+                        or tuple(windows.shape) != (n, 2) or not windows.is_contiguous() or windows.device != rays.device:
+                    raise ValueError(f"{what}: windows must be a contiguous (n, 2) float32 tensor on the rays' device")
+            shape, dtype = ((n,), torch.uint8) if occ else ((n, 8), torch.float32)
             if out is None:
-                out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
-            elif not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (n, 8) or not out.is_contiguous() \
-                    or out.device != rays.device:
-                raise ValueError("hit_rays: out must be a contiguous (n, 8) float32 tensor on the rays' device")
+                out = torch.empty(shape, dtype=dtype, device=rays.device)
+            elif type(out).__module__.split(".")[0] != "torch" or not out.is_cuda or out.dtype != dtype \
+                    or tuple(out.shape) != shape or not out.is_contiguous() or out.device != rays.device:
+                raise ValueError(f"{what}: out must be a contiguous {shape} {dtype} tensor on the rays' device")
             if stream is not None and int(stream) == 0:
-                raise ValueError("hit_rays: stream 0 is the ctx's own stream to the library; pass a stream or none")
+                raise ValueError(f"{what}: stream 0 is the ctx's own stream to the library; pass a stream or none")
             cur = side = None
             if stream is None:
                 cur = torch.cuda.current_stream(rays.device)
@@ -402,13 +426,23 @@ class FrozenHittableList:
                     side = self._torch_side
                     side.wait_stream(cur)
                     stream = side.cuda_stream
+            wp = C.c_void_p(windows.data_ptr()) if windows is not None else None
             try:
-                check(lib.om_hit_rays_device(self._ctx, C.byref(q), C.c_void_p(rays.data_ptr()), n,
-                                             C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
+                if occ:
+                    check(lib.om_occluded_rays_device(self._ctx, C.byref(q), C.c_void_p(rays.data_ptr()), wp, n,
+                                                      C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
+                elif windows is not None:
+                    check(lib.om_hit_rays_windows_device(self._ctx, C.byref(q), C.c_void_p(rays.data_ptr()), wp, n,
+                                                         C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
+                else:
+                    check(lib.om_hit_rays_device(self._ctx, C.byref(q), C.c_void_p(rays.data_ptr()), n,
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
             finally:
                 if side is not None:
                     rays.record_stream(side)                      # the allocator must not reuse them under the kernel
                     out.record_stream(side)
+                    if windows is not None:
+                        windows.record_stream(side)
                     cur.wait_stream(side)
             return out
         a = np.ascontiguousarray(rays)
@@ -417,11 +451,33 @@ class FrozenHittableList:
         else:
             a = np.ascontiguousarray(a, dtype=np.float32)
             if a.ndim != 2 or a.shape[1] != 6:
-                raise ValueError("hit_rays: need an (n, 6) float32 array")
+                raise ValueError(f"{what}: need an (n, 6) float32 array")
         n = a.shape[0]
+        wp = None
+        if windows is not None:
+            if type(windows).__module__.split(".")[0] == "torch":
+                raise ValueError(f"{what}: numpy rays need numpy windows")
+            w = np.ascontiguousarray(windows)
+            if w.dtype == L.WINDOW_DTYPE:
+                w = w.reshape(-1)
+                ok = w.shape[0] == n
+            else:
+                ok = w.dtype == np.float32 and w.ndim == 2 and w.shape == (n, 2)
+            if not ok:
+                raise ValueError(f"{what}: windows must be an (n, 2) float32 array or an n-vector of WINDOW_DTYPE")
+            wp = w.ctypes.data_as(C.c_void_p)
+        if occ:
+            res = np.empty(n, dtype=np.uint8)
+            check(lib.om_occluded_rays(self._ctx, C.byref(q), a.ctypes.data_as(C.c_void_p), wp, n,
+                                       res.ctypes.data_as(C.c_void_p)), self._ctx)
+            return res.view(np.bool_)
         hits = np.empty(n, dtype=L.HIT_DTYPE)
-        check(lib.om_hit_rays(self._ctx, C.byref(q), a.ctypes.data_as(C.c_void_p), n, hits.ctypes.data_as(C.c_void_p)),
-              self._ctx)
+        if windows is not None:
+            check(lib.om_hit_rays_windows(self._ctx, C.byref(q), a.ctypes.data_as(C.c_void_p), wp, n,
+                                          hits.ctypes.data_as(C.c_void_p)), self._ctx)
+        else:
+            check(lib.om_hit_rays(self._ctx, C.byref(q), a.ctypes.data_as(C.c_void_p), n, hits.ctypes.data_as(C.c_void_p)),
+                  self._ctx)
         return hits
 
     def query_max_grid(self):

@@ -34,6 +34,7 @@ using namespace omd;
 
 static_assert(sizeof(om_pixel_stats) == 40, "om_pixel_stats layout");
 static_assert(sizeof(om_ray) == 24 && sizeof(om_hit) == 32 && sizeof(om_query_params) == 16, "query record layouts");
+static_assert(sizeof(om_ray_window) == 8, "query window layout");
 static_assert(OM_QUERY_BLOCK == 512, "OM_QUERY_BLOCK is the wavefront workgroup size");
 static_assert(sizeof(OmAffineTest) == 64 && sizeof(OmBvhNode) == 32, "layout");
 
@@ -290,12 +291,14 @@ struct om_ctx {
     unsigned long long* progress_host = nullptr;   // om_progress: pinned host word (null: progress off)
     DevBuf frame_list;                  // tile-ordered pixel list of the full frame (wavefront path)
     DevBuf query_rays, query_hits;      // om_hit_rays staging (grown on demand, reused)
+    DevBuf query_windows, query_occ;    // om_*_windows / om_occluded_rays staging
     uint32_t frame_w = 0, frame_h = 0;
     ~om_ctx() {
         for (auto& b : scene_bufs) b.release();
         for (auto& j : jitters) j.buf.release();
         counters.release(); stats.release(); pixels.release(); frame_list.release();
         query_rays.release(); query_hits.release();
+        query_windows.release(); query_occ.release();
         view_scratch.release(); view_rgb.release(); tile_off.release(); tile_idx.release(); tile_tnear.release();
         wf.release();
         timer.release();
@@ -711,9 +714,10 @@ static om_status validate_query(om_ctx* c, const om_query_params* q, const void*
     return OM_OK;
 }
 
-om_status om_hit_rays_device(om_ctx* c, const om_query_params* q, const om_ray* dev_rays, uint32_t n, om_hit* dev_hits,
-                             void* stream) {
-    om_status s = validate_query(c, q, dev_rays, n, dev_hits);
+// One query launch: closest-hit into dev_hits, or any-hit into dev_occ (exactly one is non-null).
+static om_status launch_query(om_ctx* c, const om_query_params* q, const om_ray* dev_rays, const om_ray_window* dev_windows,
+                              uint32_t n, om_hit* dev_hits, uint8_t* dev_occ, void* stream) {
+    om_status s = validate_query(c, q, dev_rays, n, dev_hits ? (const void*)dev_hits : (const void*)dev_occ);
     if (s) return s;
     if (n == 0) return OM_OK;
     OM_HIP(c, hipSetDevice(c->device));
@@ -728,27 +732,61 @@ om_status om_hit_rays_device(om_ctx* c, const om_query_params* q, const om_ray* 
     omw::Query Q;
     Q.S = c->scene;
     Q.tmin = q->tmin; Q.tmax = q->tmax; Q.march_steps = q->march_steps;
-    Q.rays = dev_rays; Q.hits = dev_hits; Q.n = n;
+    Q.rays = dev_rays; Q.windows = dev_windows; Q.hits = dev_hits; Q.occluded = dev_occ; Q.n = n;
     Q.counters = (unsigned long long*)c->counters.p;
     Q.count = c->count_work;
     Q.trace_mode = wf_trace_mode(mode);
     const hipError_t e = omw::query(Q, st);
-    if (e != hipSuccess) return set_err(c, OM_ERR_DEVICE, std::string("om_hit_rays_device: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return set_err(c, OM_ERR_DEVICE, std::string("ray query launch: ") + hipGetErrorString(e));
     return OM_OK;
 }
 
-om_status om_hit_rays(om_ctx* c, const om_query_params* q, const om_ray* rays, uint32_t n, om_hit* hits) {
-    om_status s = validate_query(c, q, rays, n, hits);
+// Host form of either query kind: rays (and windows) in through the ctx's staging buffers, the
+// records or bytes back out, synchronous.
+static om_status host_query(om_ctx* c, const om_query_params* q, const om_ray* rays, const om_ray_window* windows, uint32_t n,
+                            om_hit* hits, uint8_t* occ) {
+    om_status s = validate_query(c, q, rays, n, hits ? (const void*)hits : (const void*)occ);
     if (s) return s;
     if (n == 0) return OM_OK;
     OM_HIP(c, hipSetDevice(c->device));
+    DevBuf& out = hits ? c->query_hits : c->query_occ;
+    const size_t out_bytes = (size_t)n * (hits ? sizeof(om_hit) : sizeof(uint8_t));
     if ((s = ensure(c, c->query_rays, (size_t)n * sizeof(om_ray))) != OM_OK) return s;
-    if ((s = ensure(c, c->query_hits, (size_t)n * sizeof(om_hit))) != OM_OK) return s;
+    if (windows && (s = ensure(c, c->query_windows, (size_t)n * sizeof(om_ray_window))) != OM_OK) return s;
+    if ((s = ensure(c, out, out_bytes)) != OM_OK) return s;
     OM_HIP(c, hipMemcpyAsync(c->query_rays.p, rays, (size_t)n * sizeof(om_ray), hipMemcpyHostToDevice, c->stream));
-    if ((s = om_hit_rays_device(c, q, (const om_ray*)c->query_rays.p, n, (om_hit*)c->query_hits.p, c->stream)) != OM_OK) return s;
-    OM_HIP(c, hipMemcpyAsync(hits, c->query_hits.p, (size_t)n * sizeof(om_hit), hipMemcpyDeviceToHost, c->stream));
+    if (windows)
+        OM_HIP(c, hipMemcpyAsync(c->query_windows.p, windows, (size_t)n * sizeof(om_ray_window), hipMemcpyHostToDevice, c->stream));
+    s = launch_query(c, q, (const om_ray*)c->query_rays.p, windows ? (const om_ray_window*)c->query_windows.p : nullptr, n,
+                     hits ? (om_hit*)out.p : nullptr, hits ? nullptr : (uint8_t*)out.p, c->stream);
+    if (s != OM_OK) return s;
+    OM_HIP(c, hipMemcpyAsync(hits ? (void*)hits : (void*)occ, out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     OM_HIP(c, hipStreamSynchronize(c->stream));
     return OM_OK;
+}
+
+om_status om_hit_rays_device(om_ctx* c, const om_query_params* q, const om_ray* dev_rays, uint32_t n, om_hit* dev_hits,
+                             void* stream) {
+    return launch_query(c, q, dev_rays, nullptr, n, dev_hits, nullptr, stream);
+}
+om_status om_hit_rays(om_ctx* c, const om_query_params* q, const om_ray* rays, uint32_t n, om_hit* hits) {
+    return host_query(c, q, rays, nullptr, n, hits, nullptr);
+}
+om_status om_hit_rays_windows_device(om_ctx* c, const om_query_params* q, const om_ray* dev_rays, const om_ray_window* dev_windows,
+                                     uint32_t n, om_hit* dev_hits, void* stream) {
+    return launch_query(c, q, dev_rays, dev_windows, n, dev_hits, nullptr, stream);
+}
+om_status om_hit_rays_windows(om_ctx* c, const om_query_params* q, const om_ray* rays, const om_ray_window* windows, uint32_t n,
+                              om_hit* hits) {
+    return host_query(c, q, rays, windows, n, hits, nullptr);
+}
+om_status om_occluded_rays_device(om_ctx* c, const om_query_params* q, const om_ray* dev_rays, const om_ray_window* dev_windows,
+                                  uint32_t n, uint8_t* dev_occluded, void* stream) {
+    return launch_query(c, q, dev_rays, dev_windows, n, nullptr, dev_occluded, stream);
+}
+om_status om_occluded_rays(om_ctx* c, const om_query_params* q, const om_ray* rays, const om_ray_window* windows, uint32_t n,
+                           uint8_t* occluded) {
+    return host_query(c, q, rays, windows, n, nullptr, occluded);
 }
 
 uint32_t om_query_max_grid(om_ctx* c) {

@@ -50,8 +50,13 @@ __device__ __forceinline__ float inv_dir(float c) {
 
 // Work counters (om_counters); compiled out (COUNT=false) of the production kernels so
 // they cost no registers — the bench counts work in a separate, identical launch.
-template <bool COUNT>
+// ANY (any-hit queries): the traversals that take this policy leave at the first
+// accepted exact test instead of looking for the closest one.  Until that acceptance `closest` is
+// still the caller's tmax, so every exact test runs with the arguments the reference loop would
+// give it, in whatever order the tree yields them; with ANY off the traversals are unchanged.
+template <bool COUNT, bool ANY_ = false>
 struct WorkT {
+    static constexpr bool ANY = ANY_;
     uint32_t prim = 0, pre = 0, march = 0;
     __device__ __forceinline__ void add_prim() { if (COUNT) prim++; }
     __device__ __forceinline__ void add_pre(uint32_t k = 1) { if (COUNT) pre += k; }
@@ -87,24 +92,24 @@ __device__ __forceinline__ int traced_brute(const OmSceneDev& S, F3 o, F3 d, flo
             if (q > B.r * B.r || -b + B.r < tmin || -b - B.r > closest) continue;
         }
         w.add_prim();
-        if (sphere_root(S.sph_test[i], o, d, tmin, closest, t)) { closest = t; best = (int)i; }
+        if (sphere_root(S.sph_test[i], o, d, tmin, closest, t)) { closest = t; best = (int)i; if (Wk::ANY) return best; }
     }
     for (uint32_t i = 0; i < S.n_cube; ++i) {
         int ax; w.add_prim();
-        if (cube_root(S.cube_test[i], o, d, tmin, closest, t, ax)) { closest = t; best = (int)(S.off_cube + i); }
+        if (cube_root(S.cube_test[i], o, d, tmin, closest, t, ax)) { closest = t; best = (int)(S.off_cube + i); if (Wk::ANY) return best; }
     }
     float ndd;
     for (uint32_t i = 0; i < S.n_tri; ++i) {
         w.add_prim();
-        if (bary_root<true>(S.tri[i], o, d, tmin, closest, t, ndd)) { closest = t; best = (int)(S.off_tri + i); }
+        if (bary_root<true>(S.tri[i], o, d, tmin, closest, t, ndd)) { closest = t; best = (int)(S.off_tri + i); if (Wk::ANY) return best; }
     }
     for (uint32_t i = 0; i < S.n_plane; ++i) {
         w.add_prim();
-        if (plane_root(S.plane[i], o, d, tmin, closest, t, ndd)) { closest = t; best = (int)(S.off_plane + i); }
+        if (plane_root(S.plane[i], o, d, tmin, closest, t, ndd)) { closest = t; best = (int)(S.off_plane + i); if (Wk::ANY) return best; }
     }
     for (uint32_t i = 0; i < S.n_para; ++i) {
         w.add_prim();
-        if (bary_root<false>(S.para[i], o, d, tmin, closest, t, ndd)) { closest = t; best = (int)(S.off_para + i); }
+        if (bary_root<false>(S.para[i], o, d, tmin, closest, t, ndd)) { closest = t; best = (int)(S.off_para + i); if (Wk::ANY) return best; }
     }
     return best;
 }
@@ -125,7 +130,10 @@ __device__ __forceinline__ int traced_bvh(const OmSceneDev& S, F3 o, F3 d, float
     // Non-finite rays take the reference loop (NaN roots are accepted there).
     if (!isfinite(o.x + o.y + o.z + d.x + d.y + d.z)) return traced_brute<false, Wk>(S, o, d, tmin, closest, w);
     int best = -1;
-    for (uint32_t k = 0; k < S.n_always; ++k) offer(S, S.always[k], o, d, tmin, closest, best, w);
+    for (uint32_t k = 0; k < S.n_always; ++k) {
+        offer(S, S.always[k], o, d, tmin, closest, best, w);
+        if (Wk::ANY && best >= 0) return best;
+    }
     if (S.n_bvh_nodes == 0) return best;
     const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
     const float t_lo = tmin * 0.5f - 1e-3f;
@@ -136,7 +144,10 @@ __device__ __forceinline__ int traced_bvh(const OmSceneDev& S, F3 o, F3 d, float
         const OmBvhNode N = S.bvh[node];
         if (N.left < 0) {
             const uint32_t first = (uint32_t)(-N.left - 1), cnt = (uint32_t)N.right;
-            for (uint32_t k = 0; k < cnt; ++k) offer(S, S.bvh_prims[first + k], o, d, tmin, closest, best, w);
+            for (uint32_t k = 0; k < cnt; ++k) {
+                offer(S, S.bvh_prims[first + k], o, d, tmin, closest, best, w);
+                if (Wk::ANY && best >= 0) return best;
+            }
         } else {
             const OmBvhNode L = S.bvh[N.left], R = S.bvh[N.right];
             w.add_pre(2);
@@ -222,6 +233,7 @@ __device__ __forceinline__ void offer_always2(const OmSceneDev& S, F3 o, F3 d, f
             } else {
                 offer_uniform(S, A.gi, o, d, tmin, closest, best, w);
             }
+            if (Wk::ANY && best >= 0) return;
             continue;
         }
         w.add_pre();
@@ -232,6 +244,7 @@ __device__ __forceinline__ void offer_always2(const OmSceneDev& S, F3 o, F3 d, f
         const float n0 = slab_near(x0, x1, y0, y1, z0, z1, t_lo);
         const float f0 = slab_far(x0, x1, y0, y1, z0, z1, t_hi);
         if (!(n0 > f0)) offer_uniform(S, A.gi, o, d, tmin, closest, best, w);
+        if (Wk::ANY && best >= 0) return;
     }
 }
 
@@ -259,7 +272,10 @@ template <class Wk>
 __device__ __forceinline__ void test_leaf(const OmAffineTest* recs, uint32_t lf, F3 o, F3 d, float tmin, float& closest,
                                           int& best, Wk& w) {
     const uint32_t first = lf >> 8, cnt = lf & 255u;
-    for (uint32_t k = 0; k < cnt; ++k) test_rec(recs[first + k], o, d, tmin, closest, best, w);
+    for (uint32_t k = 0; k < cnt; ++k) {
+        test_rec(recs[first + k], o, d, tmin, closest, best, w);
+        if (Wk::ANY && best >= 0) return;
+    }
 }
 
 
@@ -281,6 +297,7 @@ __device__ __forceinline__ int traced_sbvh(const OmSceneDev& S, const OmSkipNode
     const float nox = -o.x * ix, noy = -o.y * iy, noz = -o.z * iz;
     const float t_lo = tmin * 0.5f - 1e-3f;
     offer_always2(S, o, d, tmin, ix, iy, iz, nox, noy, noz, t_lo, closest, best, w);
+    if (Wk::ANY && best >= 0) return best;
     const uint32_t n = S.n_snodes;
     uint32_t node = 0;
     while (node < n) {
@@ -305,6 +322,7 @@ __device__ __forceinline__ int traced_sbvh(const OmSceneDev& S, const OmSkipNode
                 w.add_prim();
                 const bool h = (tag >> 31) ? cube_root(R, o, d, tmin, closest, t, ax) : sphere_root(R, o, d, tmin, closest, t);
                 if (h && (t < closest || (int)gi > best)) { closest = t; best = (int)gi; }
+                if (Wk::ANY && best >= 0) return best;
             }
         }
         node = N.skip;
@@ -694,6 +712,7 @@ __device__ __forceinline__ int traced_bvh2(const OmSceneDev& S, const Node* node
     const float nox = -o.x * ix, noy = -o.y * iy, noz = -o.z * iz;
     const float t_lo = tmin * 0.5f - 1e-3f;
     offer_always2(S, o, d, tmin, ix, iy, iz, nox, noy, noz, t_lo, closest, best, w);
+    if (Wk::ANY && best >= 0) return best;
     // slab tests of node N's two child boxes: -> h0, h1 (hit), and whether child 1 is nearer
     auto slabs = [&](const Node& N, bool& h0, bool& h1, bool& swap) {
         w.add_pre(2);
@@ -727,6 +746,7 @@ __device__ __forceinline__ int traced_bvh2(const OmSceneDev& S, const Node* node
     for (;;) {
         if (cur >= OM_LEAF) {                       // the single leaf site (16-bit codes: one compare, no and)
             test_leaf(recs, leaf_payload(S, cur, leaves), o, d, tmin, closest, best, w);
+            if (Wk::ANY && best >= 0) break;
             if (!pop()) break;
             continue;
         }
@@ -766,11 +786,13 @@ __device__ __forceinline__ int traced_bvh4(const OmSceneDev& S, const Node* node
     const float nox = -o.x * ix, noy = -o.y * iy, noz = -o.z * iz;
     const float t_lo = tmin * 0.5f - 1e-3f;
     offer_always2(S, o, d, tmin, ix, iy, iz, nox, noy, noz, t_lo, closest, best, w);
+    if (Wk::ANY && best >= 0) return best;
     uint32_t cur = 0;
     int sp = 0;
     for (;;) {
         if (cur >= OM_LEAF) {
             test_leaf(recs, leaf_payload(S, cur, leaves), o, d, tmin, closest, best, w);
+            if (Wk::ANY && best >= 0) break;
             if (sp == 0) break;
             --sp;
             cur = stk[sp * STRIDE];

@@ -97,13 +97,16 @@ struct Launch {
 // Renders P.sample_count samples of every listed pixel; returns 0 or a HIP error text.
 hipError_t render(Buffers& B, const Launch& L, hipStream_t stream, std::string& err);
 
-// One batch of closest-hit ray queries (om_hit_rays_device).
+// One batch of ray queries: closest-hit (om_hit_rays*_device) when `occluded` is
+// null, any-hit (om_occluded_rays_device, §5.16) otherwise.
 struct Query {
     OmSceneDev S;
     float tmin, tmax;
     uint32_t march_steps;
     const om_ray* rays;          // device, n records
-    om_hit* hits;                // device, n records
+    const om_ray_window* windows = nullptr;   // device, n records; null: [tmin, tmax] for every ray
+    om_hit* hits = nullptr;      // device, n records (closest-hit)
+    uint8_t* occluded = nullptr; // device, n bytes (any-hit)
     uint32_t n;
     unsigned long long* counters;
     bool count;

@@ -297,21 +297,27 @@ __device__ __forceinline__ Tracer stage_scene(const OmSceneDev& S) {   // every 
 // Closest hit of one ray (hits.rs:270-365): -> (closest, global prim index or -1).
 // MARCH is a compile-time split: the sphere-tracing code (3 SDFs + unstuck) would
 // otherwise set the register budget of every traced-only scene.
+// The traced section of variant TR over the window [tmin, closest]: -> global prim index or -1,
+// closest = the winner's root.  (Wk::ANY: the first accepted primitive, om_trace.h.)
+template <int TR, class Wk>
+__device__ __forceinline__ int trace_traced(const OmSceneDev& S, const Tracer& T, F3 o, F3 d, float tmin, float& closest, Wk& w) {
+    if (TR == TR_BVH4_LDS) return traced_bvh4<kBlk>(S, T.b4n, T.bl, T.recs, T.stk, o, d, tmin, closest, w);
+    if (TR == TR_BVH4_GLOBAL)
+        return traced_bvh4<kBlk, Wk, true>(S, T.h4l, T.bl, T.recs, T.stk, o, d, tmin, closest, w, T.h4g, T.nl);
+    if (TR == TR_BVH2_LDS)
+        return traced_bvh2<kStackDepth, kBlk, Wk, false, OmBvh2Node, 16>(S, T.b2n, T.bl, T.recs, T.stk, o, d, tmin, closest, w);
+    if (TR == TR_BVH2_GLOBAL)
+        return traced_bvh2<kStackDepth, kBlk, Wk, true>(S, T.h2l, T.bl, T.recs, T.stk, o, d, tmin, closest, w, T.h2g, T.nl);
+    if (TR == TR_SBVH_GLOBAL) return traced_sbvh(S, S.snodes, S.srecs, o, d, tmin, closest, w);
+    if (TR == TR_BVH) return traced_bvh(S, o, d, tmin, closest, w);
+    return traced_brute<TR == TR_CULLED>(S, o, d, tmin, closest, w);
+}
+
 template <int TR, bool MARCH, class Wk>
 __device__ __forceinline__ int trace(const OmSceneDev& S, const OmParamsDev& P, const Tracer& T, F3 o, F3 d,
                                      float& closest, Wk& w) {
     closest = P.tmax;
-    int best;
-    if (TR == TR_BVH4_LDS) best = traced_bvh4<kBlk>(S, T.b4n, T.bl, T.recs, T.stk, o, d, P.tmin, closest, w);
-    else if (TR == TR_BVH4_GLOBAL)
-        best = traced_bvh4<kBlk, Wk, true>(S, T.h4l, T.bl, T.recs, T.stk, o, d, P.tmin, closest, w, T.h4g, T.nl);
-    else if (TR == TR_BVH2_LDS)
-        best = traced_bvh2<kStackDepth, kBlk, Wk, false, OmBvh2Node, 16>(S, T.b2n, T.bl, T.recs, T.stk, o, d, P.tmin, closest, w);
-    else if (TR == TR_BVH2_GLOBAL)
-        best = traced_bvh2<kStackDepth, kBlk, Wk, true>(S, T.h2l, T.bl, T.recs, T.stk, o, d, P.tmin, closest, w, T.h2g, T.nl);
-    else if (TR == TR_SBVH_GLOBAL) best = traced_sbvh(S, S.snodes, S.srecs, o, d, P.tmin, closest, w);
-    else if (TR == TR_BVH) best = traced_bvh(S, o, d, P.tmin, closest, w);
-    else best = traced_brute<TR == TR_CULLED>(S, o, d, P.tmin, closest, w);
+    int best = trace_traced<TR>(S, T, o, d, P.tmin, closest, w);
     if (MARCH) {
         float tm;
         const int mg = march(S, o, d, P.tmin, P.tmax, closest, P.march_steps, tm, w);
@@ -872,6 +878,24 @@ void k_tail(OmSceneDev S, OmParamsDev P, Seg G, Queue in, const uint32_t* __rest
 // Rays (24 B) and hits (32 B) are streamed once each with the non-temporal hint, like the path
 // queues, so they do not evict nodes and leaf records from the vector L1; buffers aligned to
 // 8 / 16 B (wave-uniform test) move as dwordx2 / dwordx4.
+//
+// Per-ray windows (WIN; om_ray_window, 8 B per ray, read once like the rays): ray i
+// is answered for [tmin_i, tmax_i] instead of the call's window.  The tree culls derive
+// t_lo = tmin / 2 - 1e-3, which is above tmin for tmin < -2e-3, and nothing in them is specified for a
+// NaN bound; so a lane whose window has tmin < 0 or a NaN bound (window_edge) takes the reference
+// loop, as a lane with a non-finite ray does.  Every other window is one the culls are conservative
+// for: t_hi = tmax * 1.0001 + 1e-3 >= tmax for every tmax that can hold a root >= tmin >= 0 (+inf
+// included), and a window with tmin > tmax accepts nothing in either form.
+__device__ __forceinline__ bool window_edge(float tmin, float tmax) { return !(tmin >= 0.0f) || tmax != tmax; }
+__device__ __forceinline__ void load_query_window(const om_ray_window* __restrict__ win, uint64_t i, float& tmin, float& tmax) {
+    if (((uintptr_t)win & 7u) == 0u) {
+        const float2* w2 = (const float2*)(win + i);
+        tmin = __builtin_nontemporal_load(&w2->x); tmax = __builtin_nontemporal_load(&w2->y);
+    } else {
+        const float* w = (const float*)(win + i);
+        tmin = __builtin_nontemporal_load(w); tmax = __builtin_nontemporal_load(w + 1);
+    }
+}
 __device__ __forceinline__ void load_query_ray(const om_ray* __restrict__ rays, uint64_t i, F3& o, F3& d) {
     const float* r = (const float*)(rays + i);
     if (((uintptr_t)rays & 7u) == 0u) {
@@ -909,10 +933,10 @@ __device__ __forceinline__ void flush_counter64(unsigned long long* ctr, int slo
     if (__lane_id() == 0 && v) atomicAdd(&ctr[slot], v);
 }
 
-template <int TR, bool MARCH, bool USER, bool COUNT>
-__global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_query(OmSceneDev S, OmParamsDev P, const om_ray* __restrict__ rays,
-                                                uint32_t n, om_hit* __restrict__ hits,
-                                                unsigned long long* __restrict__ counters) {
+template <int TR, bool MARCH, bool USER, bool COUNT, bool WIN>
+__device__ __forceinline__ void query_rays(const OmSceneDev& S, const OmParamsDev& P, const om_ray* __restrict__ rays,
+                                           const om_ray_window* __restrict__ windows, uint32_t n, om_hit* __restrict__ hits,
+                                           unsigned long long* __restrict__ counters) {
     const Tracer T = stage_scene<TR>(S);
     unsigned long long segs = 0, n_prim = 0, n_pre = 0, n_march = 0;
     const uint32_t nblocks = (uint32_t)(((uint64_t)n + kBlk - 1u) / kBlk);
@@ -929,20 +953,23 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_query(OmSceneDev S, OmPa
         // infinite root is rejected where a NaN root is accepted).  A query can be handed any ray,
         // so such rays (never a whole wave in practice) run the reference loop itself.
         constexpr bool kShortcut = TR == TR_BVH2_LDS || TR == TR_BVH2_GLOBAL || TR == TR_BVH4_LDS || TR == TR_BVH4_GLOBAL;
-        if (kShortcut && !isfinite(o.x + o.y + o.z + d.x + d.y + d.z)) {
-            closest = P.tmax;
-            best = traced_brute<false>(S, o, d, P.tmin, closest, w);
+        float tmin = P.tmin, tmax = P.tmax;
+        if (WIN) load_query_window(windows, i, tmin, tmax);
+        if ((kShortcut && !isfinite(o.x + o.y + o.z + d.x + d.y + d.z)) || (WIN && window_edge(tmin, tmax))) {
+            closest = tmax;
+            best = traced_brute<false>(S, o, d, tmin, closest, w);
         } else {
-            best = trace<TR, false>(S, P, T, o, d, closest, w);
+            closest = tmax;
+            best = trace_traced<TR>(S, T, o, d, tmin, closest, w);
         }
         if (MARCH) {                                             // trace<TR, true>'s march, once for both branches
             float tm;
-            const int mg = march(S, o, d, P.tmin, P.tmax, closest, P.march_steps, tm, w);
+            const int mg = march(S, o, d, tmin, tmax, closest, P.march_steps, tm, w);
             if (mg >= 0) { best = mg; closest = tm; }
         }
         if (COUNT) { segs++; n_prim += w.prim; n_pre += w.pre; n_march += w.march; }
         F3 point = f3(0.0f, 0.0f, 0.0f), normal = point;
-        if (best >= 0) finalize<MARCH, USER>(S, best, o, d, P.tmin, closest, point, normal);
+        if (best >= 0) finalize<MARCH, USER>(S, best, o, d, tmin, closest, point, normal);
         else closest = INFINITY;
         store_query_hit(hits, i, closest, point, normal, (uint32_t)(best + 1));
     }
@@ -951,6 +978,65 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_query(OmSceneDev S, OmPa
         flush_counter64(counters, OMC_PRIM_TESTS, n_prim);
         flush_counter64(counters, OMC_PRE_TESTS, n_pre);
         flush_counter64(counters, OMC_MARCH, n_march);
+    }
+}
+template <int TR, bool MARCH, bool USER, bool COUNT>
+__global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_query(OmSceneDev S, OmParamsDev P, const om_ray* __restrict__ rays,
+                                                uint32_t n, om_hit* __restrict__ hits,
+                                                unsigned long long* __restrict__ counters) {
+    query_rays<TR, MARCH, USER, COUNT, false>(S, P, rays, nullptr, n, hits, counters);
+}
+// k_query with one window per ray (om_hit_rays_windows_device)
+template <int TR, bool MARCH, bool USER, bool COUNT>
+__global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_query_windows(OmSceneDev S, OmParamsDev P, const om_ray* __restrict__ rays,
+                                                        const om_ray_window* __restrict__ windows, uint32_t n,
+                                                        om_hit* __restrict__ hits, unsigned long long* __restrict__ counters) {
+    query_rays<TR, MARCH, USER, COUNT, true>(S, P, rays, windows, n, hits, counters);
+}
+
+// k_occluded: FrozenHittableList::hit(ray, tmin, tmax).is_some() for n rays, one byte each (0 / 1),
+// DESIGN.md §5.16.  k_query's frame (persistent grid, one staging, no later barrier) around the
+// any-hit forms of the traversals (WorkT<., true>): a lane leaves its traversal at the first accepted
+// exact test and then idles until its wave's block is done.  The answer does not depend on the
+// order of the tests: until the first acceptance every test sees closest = tmax, exactly the
+// reference loop's state before its first acceptance, and after one the result is Some whatever
+// follows.  The march runs only for lanes no traced primitive answered, with closest = tmax; there
+// is no HitRecord, so no finalize and no SDF normals.
+// The window is per lane either way (`windows` null: the call's, a wave-uniform switch); window_edge
+// windows and non-finite rays take the reference loop for every variant.
+// Each lane stores its own byte: any n and any alignment of `out` touch exactly [out, out + n).
+template <int TR, bool MARCH, bool COUNT>
+__global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_occluded(OmSceneDev S, OmParamsDev P, const om_ray* __restrict__ rays,
+                                                   const om_ray_window* __restrict__ windows, uint32_t n,
+                                                   uint8_t* __restrict__ out, unsigned long long* __restrict__ counters) {
+    const Tracer T = stage_scene<TR>(S);
+    const uint32_t nblocks = (uint32_t)(((uint64_t)n + kBlk - 1u) / kBlk);
+    for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        const uint64_t i = (uint64_t)b * kBlk + threadIdx.x;
+        WorkT<COUNT, true> w;
+        if (i < n) {
+            F3 o, d;
+            load_query_ray(rays, i, o, d);
+            float tmin = P.tmin, tmax = P.tmax;
+            if (windows) load_query_window(windows, i, tmin, tmax);
+            float closest = tmax;
+            int best;
+            if (!isfinite(o.x + o.y + o.z + d.x + d.y + d.z) || window_edge(tmin, tmax)) best = traced_brute<false>(S, o, d, tmin, closest, w);
+            else best = trace_traced<TR>(S, T, o, d, tmin, closest, w);
+            if (MARCH && best < 0) {
+                float tm;
+                best = march(S, o, d, tmin, tmax, tmax, P.march_steps, tm, w);
+            }
+            out[i] = best >= 0 ? (uint8_t)1 : (uint8_t)0;
+        }
+        // counted per block, where every lane of the wave is back: no 64-bit totals stay live across
+        // the traversals as in k_query (24 B less scratch in most marched counting variants)
+        if (COUNT) {
+            flush_counter64(counters, OMC_SEGMENTS, i < n ? 1ull : 0ull);
+            flush_counter64(counters, OMC_PRIM_TESTS, w.prim);
+            flush_counter64(counters, OMC_PRE_TESTS, w.pre);
+            flush_counter64(counters, OMC_MARCH, w.march);
+        }
     }
 }
 
@@ -1271,10 +1357,22 @@ void with_tr(int tr, F f) {
 
 template <int TR, bool MARCH, bool USER>
 void launch_query(const Query& Q, const OmParamsDev& P, uint32_t grid, uint32_t lds, hipStream_t st) {
-    if (Q.count)
+    if (Q.windows) {
+        if (Q.count)
+            hipLaunchKernelGGL((k_query_windows<TR, MARCH, USER, true>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.windows, Q.n, Q.hits, Q.counters);
+        else
+            hipLaunchKernelGGL((k_query_windows<TR, MARCH, USER, false>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.windows, Q.n, Q.hits, Q.counters);
+    } else if (Q.count)
         hipLaunchKernelGGL((k_query<TR, MARCH, USER, true>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.n, Q.hits, Q.counters);
     else
         hipLaunchKernelGGL((k_query<TR, MARCH, USER, false>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.n, Q.hits, Q.counters);
+}
+template <int TR, bool MARCH>
+void launch_occluded(const Query& Q, const OmParamsDev& P, uint32_t grid, uint32_t lds, hipStream_t st) {
+    if (Q.count)
+        hipLaunchKernelGGL((k_occluded<TR, MARCH, true>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.windows, Q.n, Q.occluded, Q.counters);
+    else
+        hipLaunchKernelGGL((k_occluded<TR, MARCH, false>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.windows, Q.n, Q.occluded, Q.counters);
 }
 
 }  // namespace
@@ -1478,8 +1576,8 @@ uint32_t query_max_grid() {
     return (uint32_t)cus * (uint32_t)(OM_WF_WAVES * 4 * 64 / kBlk);
 }
 
-// One k_query launch on `st`: the variant renders would trace with (pick_trace), MARCH / USER
-// from the world's marched and SDF-program counts.
+// One k_query (Q.hits) or k_occluded (Q.occluded) launch on `st`: the variant renders would trace
+// with (pick_trace), MARCH / USER from the world's marched and SDF-program counts.
 hipError_t query(const Query& Q, hipStream_t st) {
     if (Q.n == 0) return hipSuccess;
     const int tr = pick_trace(Q.trace_mode, Q.S);
@@ -1491,7 +1589,10 @@ hipError_t query(const Query& Q, hipStream_t st) {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)Q.n + kBlk - 1u) / kBlk, query_max_grid());
     with_tr(tr, [&](auto t) {
         constexpr int TR = decltype(t)::value;
-        if (user) launch_query<TR, true, true>(Q, P, grid, lds, st);
+        if (Q.occluded) {
+            if (march) launch_occluded<TR, true>(Q, P, grid, lds, st);
+            else launch_occluded<TR, false>(Q, P, grid, lds, st);
+        } else if (user) launch_query<TR, true, true>(Q, P, grid, lds, st);
         else if (march) launch_query<TR, true, false>(Q, P, grid, lds, st);
         else launch_query<TR, false, false>(Q, P, grid, lds, st);
     });

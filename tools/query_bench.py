@@ -18,6 +18,21 @@ spread is on record beside the medians.  Work counting is off (the production ke
     python tools/query_bench.py                  (GPU box)  -> profiles/query/query_bench.json
     python tools/query_bench.py --yardstick-only --root OTHER_TREE > parent.json    another build's yardstick
     python tools/query_bench.py --parent-json parent.json             ... recorded in the same file
+
+--occlusion: the any-hit rate (om_occluded_rays_device) beside the closest-hit rate
+(om_hit_rays_device, no windows) on the same rays: the four sets above with the call's window, and
+
+  ao         from every pinhole hit point, one random unit direction in the normal's hemisphere with a
+             per-ray window [0.001, 0.5] (closest-hit row: the same rays in [0.001, 100])
+
+The yardstick of an any-hit row is the PARENT build's closest-hit time on the same rays, taken in
+the same session: `--closest-only --root PARENT_TREE` prints one JSON line with the closest-hit rows
+alone (it needs nothing the parent lacks); run it before and after, and give both lines' file to
+--parent-json.  A set passes when the any-hit median is at most the parent's closest-hit median plus
+the parent's own min-max spread over every group of every parent run.
+
+    python tools/query_bench.py --closest-only --root PARENT_TREE >> parent.jsonl
+    python tools/query_bench.py --occlusion --parent-json parent.jsonl   -> profiles/query/occlusion_bench.json
 """
 import argparse
 import ctypes as C
@@ -94,6 +109,72 @@ def yardstick(om, L, fz, cam, stream, warmup, reps, groups):
     return out
 
 
+def occlusion_sets(om, L, fz, cam, stream):
+    """The ray sets of the --occlusion rows on the C1 world: {name: (rays, windows or None)}."""
+    g = torch.Generator(device="cuda").manual_seed(7)
+    rays = pinhole_rays(cam, "cuda")
+    shuffled = rays[torch.randperm(W * H, device="cuda", generator=g)].contiguous()
+    hits = fz.hit_rays(rays, stream=stream.cuda_stream)
+    stream.synchronize()
+    on = hits[:, 7].view(torch.int32) != 0
+    k = int(on.sum())
+    d = torch.randn((k, 3), device="cuda", generator=g)
+    secondary = torch.cat([hits[on][:, 1:4], d / d.norm(dim=1, keepdim=True)], dim=1).contiguous()
+    d = torch.randn((k, 3), device="cuda", generator=g)
+    d = d / d.norm(dim=1, keepdim=True)
+    d = torch.where((d * hits[on][:, 4:7]).sum(dim=1, keepdim=True) < 0, -d, d)      # into the normal's hemisphere
+    ao = torch.cat([hits[on][:, 1:4], d], dim=1).contiguous()
+    ao_win = torch.tensor([0.001, 0.5], dtype=torch.float32, device="cuda").repeat(k, 1).contiguous()
+    return {"pinhole": (rays, None), "shuffled": (shuffled, None), "secondary": (secondary, None), "ao": (ao, ao_win)}
+
+
+def occlusion_bench(om, L, args, stream, cam):
+    """--occlusion / --closest-only: closest-hit and (not --closest-only) any-hit rows per ray set."""
+    sp = stream.cuda_stream
+    fz = om.random_scene(0x5EED).freeze(cam)
+    L.check(L.lib.om_set_counting(fz.ctx, 0), fz.ctx)
+    out = {"build_id": L.build_id(), "device": torch.cuda.get_device_name(0), "world": "C1: S-traced random_scene(0x5EED)",
+           "frame": f"{W}x{H}", "warmup": args.warmup, "reps": args.reps, "groups": args.groups, "counting": False,
+           "closest_only": bool(args.closest_only), "sets": {}}
+    sets = occlusion_sets(om, L, fz, cam, stream)
+    mz = om.marched_scene().freeze(cam)
+    L.check(L.lib.om_set_counting(mz.ctx, 0), mz.ctx)
+    hbuf = torch.empty((W * H, 8), dtype=torch.float32, device="cuda")
+    obuf = torch.empty((W * H,), dtype=torch.uint8, device="cuda")
+    stream.synchronize()
+    jobs = [(name, fz, r, win, {}, args.reps) for name, (r, win) in sets.items()]
+    jobs.append(("marched_pinhole", mz, sets["pinhole"][0], None, {"march_steps": 256}, max(1, args.reps // 4)))
+    for name, z, r, win, kw, reps in jobs:
+        n = r.shape[0]
+        h, o = hbuf[:n], obuf[:n]
+        row = {"rays": n, "reps": reps, "window": "per ray [0.001, 0.5]" if win is not None else "call [0.001, 100]"}
+        ms = timed(stream, lambda: z.hit_rays(r, out=h, stream=sp, **kw), args.warmup, reps, args.groups)
+        row["closest_hit"] = summary(ms, n)
+        row["hit_share"] = round(float((h[:, 7].view(torch.int32) != 0).float().mean()), 4)
+        if not args.closest_only:
+            ms = timed(stream, lambda: z.occluded(r, windows=win, out=o, stream=sp, **kw), args.warmup, reps, args.groups)
+            row["any_hit"] = summary(ms, n)
+            row["occluded_share"] = round(float(o.float().mean()), 4)
+            ms = timed(stream, lambda: z.hit_rays(r, out=h, stream=sp, **kw), args.warmup, reps, args.groups)
+            row["closest_hit_again"] = summary(ms, n)
+        out["sets"][name] = row
+    mz.close()
+    fz.close()
+    if args.parent_json and not args.closest_only:
+        with open(args.parent_json) as f:
+            runs = [json.loads(ln) for ln in f.read().splitlines() if ln.startswith("{")]
+        out["parent_build"] = {"build_id": runs[0]["build_id"], "runs": len(runs)}
+        for name, row in out["sets"].items():
+            ms = [x for run in runs for x in run["sets"][name]["closest_hit"]["ms"]]
+            med, spread = statistics.median(ms), max(ms) - min(ms)
+            here = row["closest_hit"]["ms"] + row["closest_hit_again"]["ms"]
+            row["parent_closest_hit"] = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4)}
+            row["any_hit_within_parent_spread"] = bool(row["any_hit"]["ms_median"] <= med + spread)
+            row["closest_hit_vs_parent"] = {"ms_median": round(statistics.median(here), 4),
+                                            "within_parent_spread": bool(abs(statistics.median(here) - med) <= spread)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
@@ -102,8 +183,12 @@ def main():
     ap.add_argument("--root", default=ROOT, help="tree whose raytracingoneweekend_amd is measured")
     ap.add_argument("--yardstick-only", action="store_true")
     ap.add_argument("--parent-json", help="the --yardstick-only line of the parent commit's build, same session")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "query", "query_bench.json"))
+    ap.add_argument("--occlusion", action="store_true", help="any-hit rows beside closest-hit ones (occlusion_bench.json)")
+    ap.add_argument("--closest-only", action="store_true", help="the closest-hit rows of --occlusion alone, one JSON line")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "query", "occlusion_bench.json" if args.occlusion else "query_bench.json")
     if not torch.cuda.is_available():
         sys.exit("query_bench: no HIP device; rates are only measured on the GPU")
     sys.path.insert(0, os.path.abspath(args.root))
@@ -113,6 +198,14 @@ def main():
     stream = torch.cuda.Stream()
     torch.cuda.set_stream(stream)
     cam = om.default_camera(W / H)
+    if args.occlusion or args.closest_only:
+        out = occlusion_bench(om, L, args, stream, cam)
+        print(json.dumps(out))
+        if not args.closest_only:
+            os.makedirs(os.path.dirname(args.out), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
     fz = om.random_scene(0x5EED).freeze(cam)
     L.check(L.lib.om_set_counting(fz.ctx, 0), fz.ctx)
     out = {"build_id": L.build_id(), "device": torch.cuda.get_device_name(0), "world": "C1: S-traced random_scene(0x5EED)",
