@@ -7,6 +7,7 @@ the F12 save of main.rs:473-476.
     python examples/render_scene.py --width 1000 --height 666 --spp 200 --out out/
     python examples/render_scene.py --width 1000 --height 666 --pick 500 400      # what is under a pixel
     python examples/render_scene.py --width 1000 --height 666 --ao 16 0.5         # ambient occlusion, out/ao.bmp
+    python examples/render_scene.py --mesh model.obj --spp 64                     # a triangle mesh over the ground
 """
 import argparse
 import os
@@ -75,6 +76,23 @@ def ambient_occlusion(frozen, cam, W, H, samples, radius, seed):
     return np.ascontiguousarray(np.repeat(grey.reshape(H, W, 1), 3, axis=2))
 
 
+def mesh_scene(path):
+    """random_scene's ground sphere with the OBJ mesh standing on it: scaled to height 2, centred in x
+    and z, one material, added with one add_triangles call."""
+    v, f = om.load_obj(path)
+    if len(f) == 0:
+        raise SystemExit(f"{path}: no faces")
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    scale = np.float32(2.0) / max(np.float32(1e-6), (hi - lo).max())
+    mid = (lo + hi) * np.float32(0.5)
+    v = ((v - np.array([mid[0], lo[1], mid[2]], dtype=np.float32)) * scale).astype(np.float32)
+    world = om.HittableList.new()
+    world += om.Sphere.new_with_radius((0., -1000., 0.), 1000.0, om.Material.new_lambertian((0.5, 0.5, 0.5)))
+    world.add_triangles(v, f, om.Material.new_metal_fuzz((0.8, 0.7, 0.5), 0.05))
+    print(f"{path}: {len(v)} vertices, {len(f)} triangles")
+    return world
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1000)           # main.rs:125-127
@@ -86,6 +104,9 @@ def main():
                     help="take every sample of every pixel (default: retire converged pixels like the "
                          "reference's render threads, render_thread.rs:31-38,97-101)")
     ap.add_argument("--torus", action="store_true", help="include the marched torus block of main.rs:73-81")
+    ap.add_argument("--mesh", metavar="FILE.obj",
+                    help="render this Wavefront OBJ mesh (v / f lines) over the ground sphere instead of random_scene, "
+                         "scaled to height 2 and centred on the origin; --pick and --ao work on it")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default="out")
     ap.add_argument("--ppm", action="store_true", help="write PPM instead of BMP")
@@ -97,8 +118,12 @@ def main():
     args = ap.parse_args()
 
     W, H = args.width, args.height
-    world = om.random_scene_api(0x5EED, with_torus=args.torus)   # main.rs:37-100 through the API
-    cam = om.Camera.new((13.0, 2.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 20.0, W / H, 0.1, 10.0)  # main.rs:136-142
+    if args.mesh:
+        world = mesh_scene(args.mesh)
+        cam = om.Camera.new((5.0, 2.5, 6.0), (0.0, 1.0, 0.0), (0.0, 1.0, 0.0), 30.0, W / H, 0.05, 8.0)
+    else:
+        world = om.random_scene_api(0x5EED, with_torus=args.torus)   # main.rs:37-100 through the API
+        cam = om.Camera.new((13.0, 2.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 20.0, W / H, 0.1, 10.0)  # main.rs:136-142
     frozen = world.freeze(cam)
     if args.pick:
         if not (0 <= args.pick[0] < W and 0 <= args.pick[1] < H):

@@ -14,6 +14,7 @@
  *   om_world_add_cube_length    Cube::new_with_length               traced.rs:242-246
  *   om_world_add_triangle / _parallelogram  Barycentric::new3points traced.rs:148-154
  *   om_world_add_triangle_basis / _parallelogram_basis  Barycentric::new  traced.rs:135-147
+ *   om_world_add_triangles  n x Barycentric::new3points over an indexed mesh  traced.rs:148-154
  *   om_world_add_plane    InfinitePlane::new                        traced.rs:86-88
  *   om_world_add_marched_sphere / _box   struct literals            marched.rs:50-54, 79-83
  *   om_world_add_marched_torus  MarchedTorus::new                   marched.rs:116-130
@@ -163,6 +164,17 @@ om_status om_world_add_sphere_radius(om_world* w, const float center[3], float r
 om_status om_world_add_cube(om_world* w, const float local_to_world[16], const om_material* m);
 om_status om_world_add_cube_length(om_world* w, const float center[3], float length, const om_material* m);
 om_status om_world_add_triangle(om_world* w, const float origin[3], const float upoint[3], const float vpoint[3], const om_material* m);
+/* A triangle mesh with one material: n_tri triangles over an indexed vertex array.  Triangle k is
+ * Barycentric::new3points(v[i[3k]], v[i[3k+1]], v[i[3k+2]]) (traced.rs:148-154), added in order k = 0..
+ * exactly as n_tri calls of om_world_add_triangle would (same bits, same obj ids); a model with several
+ * materials is several calls.  Degenerate triangles (zero area, repeated index, non-finite vertex) are
+ * accepted and get whatever new3points computes for them.
+ * All or nothing: an index >= n_vertices, a null pointer with n_tri > 0 or an invalid material adds nothing
+ * and returns OM_ERR_INVALID.  n_tri == 0 is OM_OK.
+ * From OM_BARY_TREE_MIN (16) triangles + parallelograms on, a frozen world holds them in the leaves of its
+ * BVH trees beside the spheres and cubes: rays cost O(log n) in the mesh size, with the same answers. */
+om_status om_world_add_triangles(om_world* w, const float* vertices /* 3*n_vertices */, uint32_t n_vertices,
+                                 const uint32_t* indices /* 3*n_tri */, uint32_t n_tri, const om_material* m);
 om_status om_world_add_parallelogram(om_world* w, const float origin[3], const float upoint[3], const float vpoint[3], const om_material* m);
 om_status om_world_add_triangle_basis(om_world* w, const float origin[3], const float u[3], const float v[3], float u_length, float v_length, const om_material* m);
 om_status om_world_add_parallelogram_basis(om_world* w, const float origin[3], const float u[3], const float v[3], float u_length, float v_length, const om_material* m);

@@ -241,6 +241,13 @@ public:
                                                            t.v_length, &t.material.raw));
         return *this;
     }
+    // A triangle mesh with one material: n_tri x Triangle::new3points over an indexed vertex array
+    // (3 floats per vertex, 3 indices per triangle), in one call (om_world_add_triangles).
+    HittableList& add_triangles(const float* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_tri,
+                                const Material& material) {
+        check(om_world_add_triangles(w_, vertices, n_vertices, indices, n_tri, &material.raw));
+        return *this;
+    }
     HittableList& operator+=(const Parallelogram& p) {
         check(p.three_points ? om_world_add_parallelogram(w_, p.origin.data(), p.u.data(), p.v.data(), &p.material.raw)
                              : om_world_add_parallelogram_basis(w_, p.origin.data(), p.u.data(), p.v.data(), p.u_length,

@@ -9,7 +9,8 @@ from . import _lib
 from .api import (HIT_DTYPE, RAY_DTYPE, WINDOW_DTYPE, Camera, Cube, FrozenHittableList, HitRecord, HittableList, InfinitePlane, MarchedBox, MarchedSdf,
                   MarchedSphere, MarchedTorus, Mat4x4, Material, Parallelogram, PixelsBox, Sphere, Triangle, display, m4x4,
                   make_params, render, write_bmp, write_ppm)
-from .scenes import basic_scene, default_camera, marched_scene, random_scene, random_scene_api
+from .scenes import (basic_scene, default_camera, heightfield, icosphere, load_obj, marched_scene, random_scene,
+                     random_scene_api)
 
 PIXEL_STATS_DTYPE = _lib.PIXEL_STATS_DTYPE
 __version__ = "0.1.0"

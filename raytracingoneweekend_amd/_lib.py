@@ -119,6 +119,7 @@ EXPORTS = [
     "om_multi_render_host", "om_multi_gather", "om_multi_reset", "om_rccl_library",
     "om_hit_rays_device", "om_hit_rays", "om_world_object_material", "om_query_max_grid",
     "om_occluded_rays_device", "om_occluded_rays", "om_hit_rays_windows_device", "om_hit_rays_windows",
+    "om_world_add_triangles",
 ]
 OM_COMM_ID_BYTES = 128
 OM_TRANSPORT_RCCL, OM_TRANSPORT_LOCAL = 0, 1
@@ -172,6 +173,7 @@ def _load():
         "om_world_add_cube": (st, [vp, fp, mp]),
         "om_world_add_cube_length": (st, [vp, fp, C.c_float, mp]),
         "om_world_add_triangle": (st, [vp, fp, fp, fp, mp]),
+        "om_world_add_triangles": (st, [vp, vp, C.c_uint32, vp, C.c_uint32, mp]),
         "om_world_add_parallelogram": (st, [vp, fp, fp, fp, mp]),
         "om_world_add_triangle_basis": (st, [vp, fp, fp, fp, C.c_float, C.c_float, mp]),
         "om_world_add_parallelogram_basis": (st, [vp, fp, fp, fp, C.c_float, C.c_float, mp]),

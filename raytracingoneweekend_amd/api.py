@@ -292,6 +292,23 @@ class HittableList:
         check(prim.add_to(self._w))
         return self
 
+    def add_triangles(self, vertices, faces, material):
+        """A triangle mesh with one material (om_world_add_triangles): `vertices` (V, 3) float32,
+        `faces` (T, 3) uint32 vertex indices.  Face k becomes Triangle.new3points(v[f[k, 0]], v[f[k, 1]],
+        v[f[k, 2]], material), in order, exactly as T `world += Triangle.new3points(...)` would; one C call
+        for the whole mesh.  All or nothing: an index past the last vertex adds no triangle and raises."""
+        v = np.ascontiguousarray(vertices)
+        f = np.ascontiguousarray(faces)
+        if v.dtype != np.float32 or v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError("add_triangles: vertices must be a (V, 3) float32 array")
+        if f.dtype != np.uint32 or f.ndim != 2 or f.shape[1] != 3:
+            raise ValueError("add_triangles: faces must be a (T, 3) uint32 array")
+        if not isinstance(material, Material):
+            raise TypeError("add_triangles: material must be a Material")
+        check(lib.om_world_add_triangles(self._w, v.ctypes.data_as(C.c_void_p), v.shape[0], f.ctypes.data_as(C.c_void_p),
+                                         f.shape[0], C.byref(material.raw)))
+        return self
+
     def clear(self):
         check(lib.om_world_clear(self._w))
 

@@ -1,5 +1,6 @@
 // om_bvh.cpp — binned-SAH BVH over spheres, cubes, triangles, parallelograms.
 #include "om_bvh.h"
+#include "om_tuning.h"
 
 #include <algorithm>
 #include <cmath>
@@ -224,9 +225,11 @@ void build_bvh(const om_world& w, FrozenWorld& fw) {
 }
 
 // Stackless layout: the SAH tree over the affine primitives (spheres,
-// cubes) re-emitted in depth-first order with a skip ("miss") link per node, and the
+// cubes) and, from OM_BARY_TREE_MIN of them on, the triangles and parallelograms (§5.17),
+// re-emitted in depth-first order with a skip ("miss") link per node, and the
 // primitives' test records copied in leaf order so a leaf owns a contiguous run.
-// Everything else (planes, triangles, parallelograms, huge bounds) goes to always2.
+// Everything else (planes, huge bounds, barycentric primitives below the threshold or with a
+// non-finite value) goes to always2.
 void build_bvh4(FrozenWorld& fw);
 
 void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
@@ -243,9 +246,31 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
     };
     for (size_t i = 0; i < w.spheres.size(); ++i) add(affine_box(w.spheres[i].l2w, -1.0), fw.offsets[K_SPHERE] + (uint32_t)i);
     for (size_t i = 0; i < w.cubes.size(); ++i) add(affine_box(w.cubes[i].l2w, 0.5), fw.offsets[K_CUBE] + (uint32_t)i);
-    for (size_t i = 0; i < w.triangles.size(); ++i) always.push_back(fw.offsets[K_TRI] + (uint32_t)i);
+    // Triangles and parallelograms: from OM_BARY_TREE_MIN of them on, the ones with
+    // a finite frozen record and a finite box go to the SAH builder beside the spheres and cubes
+    // (a huge one to always2 with its box, like a huge sphere); one with a non-finite value becomes
+    // an unbounded always2 record, so no cull ever sees a NaN.  Below the threshold every one of
+    // them is in always2 with its bary_box, the layout of every world before meshes.
+    auto bary_finite = [](const OmBary& r, const Box& bx) {
+        const float* f = (const float*)&r;
+        for (size_t k = 0; k < sizeof(OmBary) / 4u; ++k) if (!std::isfinite(f[k])) return false;
+        for (int i = 0; i < 3; ++i) if (!std::isfinite(bx.lo[i]) || !std::isfinite(bx.hi[i])) return false;
+        return true;
+    };
+    std::vector<uint8_t> tri_ok(w.triangles.size()), para_ok(w.parallelograms.size());
+    size_t n_bary_ok = 0;
+    for (size_t i = 0; i < w.triangles.size(); ++i) n_bary_ok += (tri_ok[i] = bary_finite(fw.tri[i], bary_box(w.triangles[i], false)));
+    for (size_t i = 0; i < w.parallelograms.size(); ++i) n_bary_ok += (para_ok[i] = bary_finite(fw.para[i], bary_box(w.parallelograms[i], true)));
+    const bool bary_tree = n_bary_ok >= (size_t)OM_BARY_TREE_MIN;
+    for (size_t i = 0; i < w.triangles.size(); ++i) {
+        if (bary_tree && tri_ok[i]) add(bary_box(w.triangles[i], false), fw.offsets[K_TRI] + (uint32_t)i);
+        else always.push_back(fw.offsets[K_TRI] + (uint32_t)i);
+    }
     for (size_t i = 0; i < w.planes.size(); ++i) always.push_back(fw.offsets[K_PLANE] + (uint32_t)i);
-    for (size_t i = 0; i < w.parallelograms.size(); ++i) always.push_back(fw.offsets[K_PARA] + (uint32_t)i);
+    for (size_t i = 0; i < w.parallelograms.size(); ++i) {
+        if (bary_tree && para_ok[i]) add(bary_box(w.parallelograms[i], true), fw.offsets[K_PARA] + (uint32_t)i);
+        else always.push_back(fw.offsets[K_PARA] + (uint32_t)i);
+    }
     std::sort(always.begin(), always.end());
     fw.always2 = always;
     fw.always2_rec.clear();
@@ -259,9 +284,13 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
         }
         Box bx;
         bool bounded = true;
-        if (gi >= fw.offsets[K_TRI] && gi < fw.offsets[K_TRI + 1]) bx = bary_box(w.triangles[gi - fw.offsets[K_TRI]], false);
-        else if (gi >= fw.offsets[K_PARA] && gi < fw.offsets[K_PARA + 1]) bx = bary_box(w.parallelograms[gi - fw.offsets[K_PARA]], true);
-        else bounded = false;   // planes; huge spheres/cubes (their inflation would cover the scene)
+        if (gi >= fw.offsets[K_TRI] && gi < fw.offsets[K_TRI + 1]) {
+            bx = bary_box(w.triangles[gi - fw.offsets[K_TRI]], false);
+            bounded = !bary_tree || tri_ok[gi - fw.offsets[K_TRI]];
+        } else if (gi >= fw.offsets[K_PARA] && gi < fw.offsets[K_PARA + 1]) {
+            bx = bary_box(w.parallelograms[gi - fw.offsets[K_PARA]], true);
+            bounded = !bary_tree || para_ok[gi - fw.offsets[K_PARA]];
+        } else bounded = false;   // planes; huge spheres/cubes (their inflation would cover the scene)
         for (int i = 0; i < 3; ++i) {
             r.lo[i] = bounded ? std::nextafter((float)bx.lo[i], -INFINITY) : -INFINITY;
             r.hi[i] = bounded ? std::nextafter((float)bx.hi[i], INFINITY) : INFINITY;
@@ -270,6 +299,7 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
     }
     fw.snodes.clear();
     fw.srecs.clear();
+    fw.n_srec_bary = 0;
     if (b.items.empty()) return;
     uint32_t root = b.build(0, (uint32_t)b.items.size());
     // internal nodes, leaves, and internal nodes on the deepest root-to-leaf path (the compressed
@@ -309,7 +339,7 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
     std::vector<uint32_t> leaf_first(b.nodes.size(), 0);
     struct Emit {
         const Builder& b; const FrozenWorld& fw; std::vector<OmSkipNode>& out; std::vector<OmAffineTest>& recs;
-        std::vector<uint32_t>& leaf_first;
+        std::vector<uint32_t>& leaf_first; uint32_t& n_bary;
         void rec(uint32_t n) {
             const OmBvhNode& src = b.nodes[n];
             const uint32_t idx = (uint32_t)out.size();
@@ -323,11 +353,13 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
                 leaf_first[n] = (uint32_t)recs.size();
                 for (uint32_t k = 0; k < cnt; ++k) {
                     const uint32_t gi = b.order[first + k];
-                    const bool cube = gi >= fw.offsets[K_CUBE];
-                    OmAffineTest t = cube ? fw.cube_test[gi - fw.offsets[K_CUBE]] : fw.sph_test[gi];
-                    const uint32_t tag = gi | (cube ? 0x80000000u : 0u);
+                    const bool bary = gi >= fw.offsets[K_TRI];       // a slot with only its tag (om_layout.h)
+                    const bool cube = !bary && gi >= fw.offsets[K_CUBE];
+                    OmAffineTest t = bary ? OmAffineTest{} : cube ? fw.cube_test[gi - fw.offsets[K_CUBE]] : fw.sph_test[gi];
+                    const uint32_t tag = gi | (cube ? OM_REC_CUBE : 0u) | (bary ? OM_REC_BARY : 0u);
                     std::memcpy(&t.pad, &tag, 4);
                     recs.push_back(t);
+                    n_bary += bary ? 1u : 0u;
                 }
             } else {
                 rec((uint32_t)src.left);
@@ -335,7 +367,7 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
             }
             out[idx].skip = (uint32_t)out.size();
         }
-    } e{b, fw, fw.snodes, fw.srecs, leaf_first};
+    } e{b, fw, fw.snodes, fw.srecs, leaf_first, fw.n_srec_bary};
     e.rec(root);
 
     // compressed BVH2: both child boxes in the parent (one 64-B read per visit), emitted
@@ -425,9 +457,11 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
     for (const OmAffineTest& t : fw.srecs) {
         uint32_t tag;
         std::memcpy(&tag, &t.pad, 4);
-        const uint32_t gi = tag & 0x7FFFFFFFu;
-        const Box bx = (tag >> 31) ? affine_box(w.cubes[gi - fw.offsets[K_CUBE]].l2w, 0.5)
-                                   : affine_box(w.spheres[gi].l2w, -1.0);
+        const uint32_t gi = tag & OM_REC_GI;
+        const Box bx = (tag & OM_REC_BARY) ? (gi >= fw.offsets[K_PARA] ? bary_box(w.parallelograms[gi - fw.offsets[K_PARA]], true)
+                                                                       : bary_box(w.triangles[gi - fw.offsets[K_TRI]], false))
+                     : (tag & OM_REC_CUBE) ? affine_box(w.cubes[gi - fw.offsets[K_CUBE]].l2w, 0.5)
+                                           : affine_box(w.spheres[gi].l2w, -1.0);
         for (int i = 0; i < 3; ++i) fw.srec_box.push_back(std::nextafter((float)bx.lo[i], -INFINITY));
         for (int i = 0; i < 3; ++i) fw.srec_box.push_back(std::nextafter((float)bx.hi[i], INFINITY));
     }

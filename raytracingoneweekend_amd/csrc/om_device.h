@@ -168,8 +168,9 @@ __device__ __forceinline__ bool plane_root(const OmPlane& P, F3 o, F3 d, float t
     return !(root == INFINITY || root < tmin || root > tmax);
 }
 // Barycentric::hit_aux (traced.rs:176-200), TRI: check_lambdas_triangle else _parallelogram.
-template <bool TRI>
-__device__ __forceinline__ bool bary_root(const OmBary& B, F3 o, F3 d, float tmin, float tmax, float& root, float& ndd) {
+// The kind as a value: the tree leaves' records (om_trace.h test_rec) hold both kinds.
+__device__ __forceinline__ bool bary_root_kind(const OmBary& B, const bool TRI, F3 o, F3 d, float tmin, float tmax, float& root,
+                                               float& ndd) {
     float r, nd;
     plane_isect(ld3(B.uxv), ld3(B.origin), o, d, r, nd);
     if (r == INFINITY || r < tmin || r > tmax) return false;
@@ -187,6 +188,10 @@ __device__ __forceinline__ bool bary_root(const OmBary& B, F3 o, F3 d, float tmi
     if (!ok) return false;
     root = r; ndd = nd;
     return true;
+}
+template <bool TRI>
+__device__ __forceinline__ bool bary_root(const OmBary& B, F3 o, F3 d, float tmin, float tmax, float& root, float& ndd) {
+    return bary_root_kind(B, TRI, o, d, tmin, tmax, root, ndd);
 }
 
 // ---------------------------------------------------------------- marched.rs

@@ -19,6 +19,13 @@ struct OM_ALIGN16 OmAffineTest {
     float dz[3];
     float pad;
 };
+// A leaf record of the SBVH / BVH2 / BVH4 (srecs) is an OmAffineTest whose `pad` carries the tag
+// gi | kind bits: the Sphere's or Cube's own test record, or (OM_REC_BARY, worlds with at least
+// OM_BARY_TREE_MIN of them) a slot holding only the tag of a triangle or
+// parallelogram, whose exact test reads its OmBary from tri / para by gi.  gi < 2^30 (checked at upload).
+#define OM_REC_CUBE 0x80000000u
+#define OM_REC_BARY 0x40000000u
+#define OM_REC_GI 0x3FFFFFFFu
 struct OM_ALIGN16 OmAffineHit {
     float l2w[12];
     float lz[3];  // l2w[i][3] * 0.0f
@@ -206,7 +213,8 @@ struct OmSceneDev {
     const uint32_t* always;       // their global indices (ascending)
     // type offsets of the global index space
     uint32_t off_cube, off_tri, off_plane, off_para, off_msph, off_mbox, off_mtor, off_msdf, n_total;
-    // stackless BVH over the affine primitives (records carry gi | cube<<31 in `pad`)
+    // stackless BVH over the affine primitives, and the barycentric ones of worlds with at least
+    // OM_BARY_TREE_MIN of them (records carry gi | OM_REC_CUBE / OM_REC_BARY in `pad`)
     const OmSkipNode* snodes; const OmAffineTest* srecs; const uint32_t* always2;
     uint32_t n_snodes, n_srecs, n_always2;
     uint32_t lds_bytes;           // dynamic LDS the staged kernel needs (0 = scene too big: global path)
@@ -226,6 +234,7 @@ struct OmSceneDev {
     uint32_t n_b4nodes;
     uint32_t b4_lds_bytes;        // node bytes when they fit the LDS budget, else 0 (global nodes)
     uint32_t b4_stack;            // lane-stack entries: 3 per level + 3 for the unconditional pushes
+    uint32_t n_srec_bary;         // OM_REC_BARY records in srecs (0: the traversals run without the barycentric leaf test)
 };
 
 struct OmCamDev {

@@ -64,8 +64,9 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 extern __shared__ __attribute__((aligned(16))) uint4 om_lds[];
 
 // MARCH is a compile-time split (as in the wavefront): traced-only scenes do not carry
-// the sphere-tracing code's registers.
-template <int MODE, int BLOCK, bool COUNT, bool MARCH>
+// the sphere-tracing code's registers.  BARY likewise (SBVH / BVH2 modes): worlds whose leaves
+// hold triangles / parallelograms run the leaf test with the barycentric case.
+template <int MODE, int BLOCK, bool COUNT, bool MARCH, bool BARY = false>
 __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 ? 4 : 1)) void render_kernel(OmSceneDev S, OmCamDev C, OmParamsDev P,
                                                        const float2* __restrict__ jitter,
                                                        om_pixel_stats* __restrict__ stats,
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(BLOCK, (BLOCK >= 512 ? 4 : 1)) void render_kernel(O
     Rng g; g.s = 0; g.k = 0;
     uint32_t seg = 0, first_id = 0;
     float depthf = 0.0f;
-    WorkT<COUNT> w;
+    WorkT<COUNT, false, BARY> w;
     uint32_t n_samples = 0, n_segments = 0, credited = 0;
 
     for (;;) {
@@ -400,6 +401,19 @@ void go(bool count, uint64_t threads, uint32_t lds, hipStream_t stream, const Om
         const OmParamsDev& P, const float2* jt, om_pixel_stats* st, const uint32_t* px, unsigned long long* ctr) {
     const uint32_t blocks = (uint32_t)((threads + BLOCK - 1) / BLOCK);
     const bool march = (S.n_msph + S.n_mbox + S.n_mtor + S.n_msdf) != 0u;
+    if constexpr (MODE == MODE_SBVH_LDS || MODE == MODE_SBVH_GLOBAL || MODE == MODE_BVH2) {
+        if (S.n_srec_bary) {                                   // triangles / parallelograms in the leaves
+            if (count && march)
+                hipLaunchKernelGGL((render_kernel<MODE, BLOCK, true, true, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
+            else if (count)
+                hipLaunchKernelGGL((render_kernel<MODE, BLOCK, true, false, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
+            else if (march)
+                hipLaunchKernelGGL((render_kernel<MODE, BLOCK, false, true, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
+            else
+                hipLaunchKernelGGL((render_kernel<MODE, BLOCK, false, false, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
+            return;
+        }
+    }
     if (count && march)
         hipLaunchKernelGGL((render_kernel<MODE, BLOCK, true, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
     else if (count)
@@ -655,6 +669,10 @@ om_status om_upload_world(om_ctx* c, const om_world* w) {
     if (plan.b4_ok && (s = upload(c, fw.b4h, &S.b4h)) != OM_OK) return s;
     S.n_b4nodes = plan.b4_ok ? (uint32_t)fw.b4nodes.size() : 0u;
     S.b4_stack = plan.b4_stack; S.b4_lds_bytes = plan.b4_lds_bytes;
+    // barycentric leaf records carry gi in 30 bits beside the two kind bits (om_layout.h OM_REC_GI)
+    S.n_srec_bary = fw.n_srec_bary;
+    if (fw.n_srec_bary && fw.offsets[om::K_N] > OM_REC_GI)
+        return set_err(c, OM_ERR_UNSUPPORTED, "om_upload_world: a world with triangles in its trees holds at most 2^30 objects");
     OM_HIP(c, hipStreamSynchronize(c->stream));
     c->have_world = true;
     return OM_OK;

@@ -54,9 +54,13 @@ __device__ __forceinline__ float inv_dir(float c) {
 // accepted exact test instead of looking for the closest one.  Until that acceptance `closest` is
 // still the caller's tmax, so every exact test runs with the arguments the reference loop would
 // give it, in whatever order the tree yields them; with ANY off the traversals are unchanged.
-template <bool COUNT, bool ANY_ = false>
+// BARY: the leaf records may be triangles / parallelograms (OM_REC_BARY), so the
+// leaf test carries the barycentric case; chosen at launch from the uploaded world (n_srec_bary),
+// like MARCH / USER.  Off, the traversals are the code of worlds whose leaves hold only spheres and cubes.
+template <bool COUNT, bool ANY_ = false, bool BARY_ = false>
 struct WorkT {
     static constexpr bool ANY = ANY_;
+    static constexpr bool BARY = BARY_;
     uint32_t prim = 0, pre = 0, march = 0;
     __device__ __forceinline__ void add_prim() { if (COUNT) prim++; }
     __device__ __forceinline__ void add_pre(uint32_t k = 1) { if (COUNT) pre += k; }
@@ -248,11 +252,33 @@ __device__ __forceinline__ void offer_always2(const OmSceneDev& S, F3 o, F3 d, f
     }
 }
 
-// One leaf record (Sphere/Cube test record, tag bit 31 = cube), brute-force tie rule.
+// A barycentric leaf record (tag & OM_REC_BARY, Wk::BARY worlds): bary_root with the brute loop's
+// arguments on the primitive's OmBary, which the lane reads from tri / para by gi (the 64-B slot
+// holds only the tag), and the brute-force tie rule.  The read goes through the vector L1 like the
+// Sphere / Cube records of a leaf: the tag is per lane, and every lane that enters the leaf needs
+// the same 64 B, so a wave-uniform leaf costs one line.
+template <class Wk>
+__device__ __forceinline__ void test_bary_rec(const OmSceneDev& S, uint32_t tag, F3 o, F3 d, float tmin, float& closest,
+                                              int& best, Wk& w) {
+    const uint32_t gi = tag & OM_REC_GI;
+    const bool tri = gi < S.off_para;
+    const OmBary* B = tri ? S.tri + (gi - S.off_tri) : S.para + (gi - S.off_para);
+    float t, ndd;
+    w.add_prim();
+    const bool h = bary_root_kind(*B, tri, o, d, tmin, closest, t, ndd);
+    if (h && (t < closest || (int)gi > best)) { closest = t; best = (int)gi; }
+}
+
+// One leaf record (Sphere/Cube test record, tag bit 31 = cube; Wk::BARY: or a barycentric slot, bit
+// 30), brute-force tie rule.
 template <bool FASTREJ = false, class Wk>
-__device__ __forceinline__ void test_rec(const OmAffineTest& R, F3 o, F3 d, float tmin, float& closest, int& best, Wk& w) {
+__device__ __forceinline__ void test_rec(const OmSceneDev& S, const OmAffineTest& R, F3 o, F3 d, float tmin, float& closest,
+                                         int& best, Wk& w) {
     uint32_t tag;
     __builtin_memcpy(&tag, &R.pad, 4);
+    if constexpr (Wk::BARY) {
+        if (tag & OM_REC_BARY) { test_bary_rec(S, tag, o, d, tmin, closest, best, w); return; }
+    }
     const uint32_t gi = tag & 0x7FFFFFFFu;
     float t;
     int ax;
@@ -269,11 +295,11 @@ __device__ __forceinline__ uint32_t leaf_payload(const OmSceneDev& S, uint32_t c
 
 // Leaf of the BVH2/BVH4: its records, tested in place.
 template <class Wk>
-__device__ __forceinline__ void test_leaf(const OmAffineTest* recs, uint32_t lf, F3 o, F3 d, float tmin, float& closest,
-                                          int& best, Wk& w) {
+__device__ __forceinline__ void test_leaf(const OmSceneDev& S, const OmAffineTest* recs, uint32_t lf, F3 o, F3 d, float tmin,
+                                          float& closest, int& best, Wk& w) {
     const uint32_t first = lf >> 8, cnt = lf & 255u;
     for (uint32_t k = 0; k < cnt; ++k) {
-        test_rec(recs[first + k], o, d, tmin, closest, best, w);
+        test_rec(S, recs[first + k], o, d, tmin, closest, best, w);
         if (Wk::ANY && best >= 0) return;
     }
 }
@@ -313,6 +339,15 @@ __device__ __forceinline__ int traced_sbvh(const OmSceneDev& S, const OmSkipNode
             if (N.leaf == 0xFFFFFFFFu) { node++; continue; }
             const uint32_t first = N.leaf >> 8, cnt = N.leaf & 255u;
             for (uint32_t k = 0; k < cnt; ++k) {
+                if constexpr (Wk::BARY) {                      // (a barycentric slot: only its tag is read)
+                    uint32_t btag;
+                    __builtin_memcpy(&btag, &recs[first + k].pad, 4);
+                    if (btag & OM_REC_BARY) {
+                        test_bary_rec(S, btag, o, d, tmin, closest, best, w);
+                        if (Wk::ANY && best >= 0) return best;
+                        continue;
+                    }
+                }
                 const OmAffineTest R = recs[first + k];
                 uint32_t tag;
                 __builtin_memcpy(&tag, &R.pad, 4);
@@ -634,8 +669,8 @@ namespace omd {
 
 // Compressed-BVH2 traversal: one 64-B node read gives both child
 // boxes; near child first, the far one pushed on a per-lane u16 stack that lives in
-// LDS (stk[level * STRIDE]) — no scratch memory.  Leaves hold only Sphere/Cube
-// records (everything else is in always2).  Box tests only choose which exact tests
+// LDS (stk[level * STRIDE]) — no scratch memory.  Leaves hold Sphere/Cube records and,
+// in Wk::BARY worlds, triangle / parallelogram slots (everything else is in always2).  Box tests only choose which exact tests
 // run (FMA allowed, conservative, see traced_sbvh); the acceptance keeps the
 // brute-force tie rule, so the winner is bit-identical to hits.rs:274-285.
 // The stack needs one entry per internal level (om_upload_world sizes it to the tree).
@@ -682,11 +717,11 @@ __device__ __forceinline__ int traced_tiles(const OmSceneDev& S, const uint32_t*
         for (; k < e; ++k) {
             const uint32_t r = rec_at(k);
             if (tnear && __ballot(!(closest < uniform_load(tnear + r))) == 0) break;
-            test_rec<true>(uniform_load(S.srecs + r), o, d, tmin, closest, best, w);
+            test_rec<true>(S, uniform_load(S.srecs + r), o, d, tmin, closest, best, w);
         }
     } else {
         const uint32_t e = toff[tile + 1];
-        for (uint32_t k = toff[tile]; k < e; ++k) test_rec(S.srecs[tidx[k]], o, d, tmin, closest, best, w);
+        for (uint32_t k = toff[tile]; k < e; ++k) test_rec(S, S.srecs[tidx[k]], o, d, tmin, closest, best, w);
     }
     return best;
 }
@@ -745,7 +780,7 @@ __device__ __forceinline__ int traced_bvh2(const OmSceneDev& S, const Node* node
     // C1 ran 14% slower (r04)
     for (;;) {
         if (cur >= OM_LEAF) {                       // the single leaf site (16-bit codes: one compare, no and)
-            test_leaf(recs, leaf_payload(S, cur, leaves), o, d, tmin, closest, best, w);
+            test_leaf(S, recs, leaf_payload(S, cur, leaves), o, d, tmin, closest, best, w);
             if (Wk::ANY && best >= 0) break;
             if (!pop()) break;
             continue;
@@ -791,7 +826,7 @@ __device__ __forceinline__ int traced_bvh4(const OmSceneDev& S, const Node* node
     int sp = 0;
     for (;;) {
         if (cur >= OM_LEAF) {
-            test_leaf(recs, leaf_payload(S, cur, leaves), o, d, tmin, closest, best, w);
+            test_leaf(S, recs, leaf_payload(S, cur, leaves), o, d, tmin, closest, best, w);
             if (Wk::ANY && best >= 0) break;
             if (sp == 0) break;
             --sp;

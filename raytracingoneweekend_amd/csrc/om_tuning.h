@@ -125,3 +125,13 @@
 #ifndef OM_B2_NODE_STRIDE
 #define OM_B2_NODE_STRIDE 80
 #endif
+// Triangles + parallelograms (counted together; only the bounded ones with finite records) from
+// which build_skip_bvh puts them into the SBVH / BVH2 / BVH4 leaves beside the spheres and cubes
+// (DESIGN.md §5.17); a world with fewer keeps them in always2 and its frozen layout byte for byte.
+// NOT a measured crossover: 16 is above every world the repository renders, tests or benchmarks
+// with barycentric primitives in always2 (random_scene, tie_scene and kitchen_sink hold 2 each), so
+// that tests/test_tree_regimes.py, the launch counts pinned in tests/test_gpu_production_shapes.py
+// and bench.py's four configs run exactly what they ran before.  The crossover itself is open.
+#ifndef OM_BARY_TREE_MIN
+#define OM_BARY_TREE_MIN 16
+#endif

@@ -61,7 +61,14 @@ namespace {
 
 constexpr uint32_t kNoSample = 0xFFFFFFFFu;
 enum { TR_BRUTE = 1, TR_CULLED = 2, TR_BVH = 3, TR_SBVH_LDS = 4, TR_SBVH_GLOBAL = 5, TR_BVH2_LDS = 6, TR_BVH2_GLOBAL = 7,
-       TR_BVH4_LDS = 8, TR_BVH4_GLOBAL = 9 };
+       TR_BVH4_LDS = 8, TR_BVH4_GLOBAL = 9,
+       // flag on a tree variant (TR_SBVH_GLOBAL, TR_BVH2_*, TR_BVH4_*): the world's leaves hold triangles /
+       // parallelograms (OmSceneDev::n_srec_bary), so the kernels are the instantiations
+       // whose leaf test carries the barycentric case (WorkT's BARY); every other world runs the
+       // instantiations without the flag, the code it ran before meshes
+       TR_BARY = 16 };
+constexpr int tr_base(int tr) { return tr & (TR_BARY - 1); }      // the variant without the flag
+constexpr bool tr_bary(int tr) { return (tr & TR_BARY) != 0; }
 #define OM_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(OM_WF_WAVES, OM_WF_WAVES)))   // occupancy request (waves per SIMD)
 constexpr int kBlk = OM_WF_BLOCK;                                 // workgroup = one queue segment
 constexpr int kStackDepth = 24;                                   // BVH2 per-lane LDS stack bound (entries)
@@ -75,7 +82,7 @@ static_assert(kB2LdsBudget / sizeof(OmBvh2Node) * (kB2Stride / 16u) < OM_LEAF, "
 // S-traced: 9 KiB per 512-lane workgroup instead of 24 KiB at the 24-entry bound).
 template <int TR>
 __host__ __device__ inline uint32_t stack_bytes(const OmSceneDev& S) {
-    return kBlk * ((TR == TR_BVH4_LDS || TR == TR_BVH4_GLOBAL) ? S.b4_stack : S.b2_stack) * 2u;
+    return kBlk * ((tr_base(TR) == TR_BVH4_LDS || tr_base(TR) == TR_BVH4_GLOBAL) ? S.b4_stack : S.b2_stack) * 2u;
 }
 // LDS bytes of a BVH2 staged whole (TR_BVH2_LDS): padded nodes + leaf table
 __host__ __device__ inline uint32_t b2_stage_bytes(const OmSceneDev& S) {
@@ -117,7 +124,7 @@ __host__ __device__ inline uint32_t hyb4_nodes(const OmSceneDev& S) {
 using MarchedC2Lds = MarchedExactLds<2, 1, 1>;
 enum { MV_ARRAYS = 0, MV_EXACT_C2_LDS = 1 };
 template <int TR>
-__host__ __device__ constexpr bool exact_view_built() { return TR == TR_BRUTE || TR == TR_BVH2_LDS; }
+__host__ __device__ constexpr bool exact_view_built() { return TR == TR_BRUTE || TR == TR_BVH2_LDS; }   // (not the TR_BARY forms)
 // Segment capacity rounded up to whole waves, so that a bounce-0 wave is exactly one 8x8 tile of
 // one sample (tile-ordered pixel lists hold whole tiles).
 __host__ __device__ inline uint32_t seg_capacity(uint64_t paths, uint32_t nseg) {
@@ -249,8 +256,9 @@ struct Tracer {
     uint16_t* stk;
 };
 
-template <int TR, uint32_t STACKS = 1>
+template <int TRF, uint32_t STACKS = 1>
 __device__ __forceinline__ Tracer stage_scene(const OmSceneDev& S) {   // every thread of the block calls it
+    constexpr int TR = tr_base(TRF);                                    // (staging does not depend on TR_BARY)
     Tracer t;
     t.stk = (uint16_t*)wf_lds + threadIdx.x;
     t.b2n = S.b2nodes; t.b4n = S.b4nodes; t.bl = S.b2leaves; t.recs = S.srecs;
@@ -299,8 +307,10 @@ __device__ __forceinline__ Tracer stage_scene(const OmSceneDev& S) {   // every 
 // otherwise set the register budget of every traced-only scene.
 // The traced section of variant TR over the window [tmin, closest]: -> global prim index or -1,
 // closest = the winner's root.  (Wk::ANY: the first accepted primitive, om_trace.h.)
-template <int TR, class Wk>
+template <int TRF, class Wk>
 __device__ __forceinline__ int trace_traced(const OmSceneDev& S, const Tracer& T, F3 o, F3 d, float tmin, float& closest, Wk& w) {
+    constexpr int TR = tr_base(TRF);
+    static_assert(Wk::BARY == tr_bary(TRF), "the work policy carries the variant's TR_BARY flag");
     if (TR == TR_BVH4_LDS) return traced_bvh4<kBlk>(S, T.b4n, T.bl, T.recs, T.stk, o, d, tmin, closest, w);
     if (TR == TR_BVH4_GLOBAL)
         return traced_bvh4<kBlk, Wk, true>(S, T.h4l, T.bl, T.recs, T.stk, o, d, tmin, closest, w, T.h4g, T.nl);
@@ -447,7 +457,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
     __syncthreads();
     const Tracer T = HIT ? Tracer{} : stage_scene<TR>(S);
     const uint32_t depth_cap = P.max_depth > 1u ? P.max_depth : 1u;
-    WorkT<COUNT> w;
+    WorkT<COUNT, false, tr_bary(TR)> w;
     uint32_t segs = 0;
     const uint32_t lane = __lane_id();
     for (uint32_t chunk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); chunk * 64u < n;) {   // wave-uniform
@@ -470,7 +480,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
                 if (HIT) {
                     const float2 h = hitbuf[i];
                     closest = h.x; best = __float_as_int(h.y);
-                } else if (FIRST && (TR == TR_BVH2_LDS || TR == TR_BVH2_GLOBAL) && R.tile_off) {
+                } else if (FIRST && (tr_base(TR) == TR_BVH2_LDS || tr_base(TR) == TR_BVH2_GLOBAL) && R.tile_off) {
                     const uint32_t line = p_pixel / P.width;
                     const uint32_t tile = (p_pixel - line * P.width) / 8u + (line / 8u) * P.tiles_x;
                     closest = P.tmax;
@@ -615,7 +625,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_march(OmSceneDev S, OmPa
     if (threadIdx.x == 0) next = kBlk;
     __syncthreads();
     const Tracer T = stage_scene<TR>(S);
-    WorkT<COUNT> w;
+    WorkT<COUNT, false, tr_bary(TR)> w;
     if constexpr (VIEW == MV_EXACT_C2_LDS) {
         __shared__ MarchedC2Lds::Block mblock;
         march_lanes<TR, COUNT>(S, P, T, MarchedC2Lds(S, &mblock), in, seg0, n, next, hit, w);
@@ -759,7 +769,7 @@ void k_tail_march(OmSceneDev S, OmParamsDev P, Seg G, Queue in,
     if (total == 0) return;
     const Tracer T = stage_scene<TR>(S);
     const TailSrc src{in, pre, s0, SPB, G.segcap};
-    WorkT<COUNT> w;
+    WorkT<COUNT, false, tr_bary(TR)> w;
     uint32_t segs = 0;
     if constexpr (VIEW == MV_EXACT_C2_LDS) {
         __shared__ MarchedC2Lds::Block mblock;
@@ -823,7 +833,7 @@ void k_tail(OmSceneDev S, OmParamsDev P, Seg G, Queue in, const uint32_t* __rest
     const Tracer T = stage_scene<TR>(S);
     const uint32_t depth_cap = P.max_depth > 1u ? P.max_depth : 1u;
     const TailSrc src{in, pre, 0u, G.nseg, G.segcap};
-    WorkT<COUNT> w;
+    WorkT<COUNT, false, tr_bary(TR)> w;
     uint32_t segs = 0;
     const uint32_t lanes = gridDim.x * kBlk;                  // paths [0, lanes) are dealt, the rest claimed
     const uint32_t round = (wave + kWaves - blockIdx.x % kWaves) % kWaves;
@@ -943,7 +953,7 @@ __device__ __forceinline__ void query_rays(const OmSceneDev& S, const OmParamsDe
     for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {      // (b + gridDim.x <= 2^23 + 2^23: no wrap)
         const uint64_t i = (uint64_t)b * kBlk + threadIdx.x;
         if (i >= n) continue;
-        WorkT<COUNT> w;                                          // this ray's work
+        WorkT<COUNT, false, tr_bary(TR)> w;                      // this ray's work
         F3 o, d;
         load_query_ray(rays, i, o, d);
         float closest;
@@ -952,7 +962,8 @@ __device__ __forceinline__ void query_rays(const OmSceneDev& S, const OmParamsDe
         // reference loop's answer when a component is NaN but not always when one is infinite (an
         // infinite root is rejected where a NaN root is accepted).  A query can be handed any ray,
         // so such rays (never a whole wave in practice) run the reference loop itself.
-        constexpr bool kShortcut = TR == TR_BVH2_LDS || TR == TR_BVH2_GLOBAL || TR == TR_BVH4_LDS || TR == TR_BVH4_GLOBAL;
+        constexpr int T0 = tr_base(TR);
+        constexpr bool kShortcut = T0 == TR_BVH2_LDS || T0 == TR_BVH2_GLOBAL || T0 == TR_BVH4_LDS || T0 == TR_BVH4_GLOBAL;
         float tmin = P.tmin, tmax = P.tmax;
         if (WIN) load_query_window(windows, i, tmin, tmax);
         if ((kShortcut && !isfinite(o.x + o.y + o.z + d.x + d.y + d.z)) || (WIN && window_edge(tmin, tmax))) {
@@ -1013,7 +1024,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_occluded(OmSceneDev S, O
     const uint32_t nblocks = (uint32_t)(((uint64_t)n + kBlk - 1u) / kBlk);
     for (uint32_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
         const uint64_t i = (uint64_t)b * kBlk + threadIdx.x;
-        WorkT<COUNT, true> w;
+        WorkT<COUNT, true, tr_bary(TR)> w;
         if (i < n) {
             F3 o, d;
             load_query_ray(rays, i, o, d);
@@ -1326,14 +1337,17 @@ int pick_trace(int trace_mode, const OmSceneDev& S) {
     // which every k_march / k_tail wave would then carry for nothing (C2: 1785 vs 1649, r02_v8)
     if (tr == TR_BVH2_LDS)
         tr = S.n_b2nodes == 0 ? (S.n_bvh_nodes <= 1u ? TR_BRUTE : TR_BVH) : (S.b2_lds_bytes ? TR_BVH2_LDS : TR_BVH2_GLOBAL);
+    // triangles / parallelograms in the leaves: the tree variants' TR_BARY instantiations
+    const int bary = S.n_srec_bary ? TR_BARY : 0;
     switch (tr) {
-        case TR_BRUTE: case TR_CULLED: case TR_BVH: case TR_SBVH_GLOBAL: case TR_BVH2_LDS: case TR_BVH4_LDS: case TR_BVH4_GLOBAL:
-            return tr;
-        default: return TR_BVH2_GLOBAL;
+        case TR_BRUTE: case TR_CULLED: case TR_BVH: return tr;
+        case TR_SBVH_GLOBAL: case TR_BVH2_LDS: case TR_BVH4_LDS: case TR_BVH4_GLOBAL: return tr | bary;
+        default: return TR_BVH2_GLOBAL | bary;
     }
 }
 // dynamic LDS bytes of a workgroup that stages variant `tr` (stage_scene's [stack][nodes][leaf table])
-uint32_t trace_lds(int tr, const OmSceneDev& S) {
+uint32_t trace_lds(int trf, const OmSceneDev& S) {
+    const int tr = tr_base(trf);
     return tr == TR_BVH2_LDS ? stack_bytes<TR_BVH2_LDS>(S) + b2_stage_bytes(S)
          : tr == TR_BVH2_GLOBAL ? stack_bytes<TR_BVH2_GLOBAL>(S) + hyb_nodes(S) * (uint32_t)sizeof(OmBvh2NodeH)
          : tr == TR_BVH4_LDS ? stack_bytes<TR_BVH4_LDS>(S) + S.b4_lds_bytes
@@ -1351,6 +1365,11 @@ void with_tr(int tr, F f) {
         case TR_BVH2_LDS: f(std::integral_constant<int, TR_BVH2_LDS>{}); break;
         case TR_BVH4_LDS: f(std::integral_constant<int, TR_BVH4_LDS>{}); break;
         case TR_BVH4_GLOBAL: f(std::integral_constant<int, TR_BVH4_GLOBAL>{}); break;
+        case TR_SBVH_GLOBAL | TR_BARY: f(std::integral_constant<int, TR_SBVH_GLOBAL | TR_BARY>{}); break;
+        case TR_BVH2_LDS | TR_BARY: f(std::integral_constant<int, TR_BVH2_LDS | TR_BARY>{}); break;
+        case TR_BVH2_GLOBAL | TR_BARY: f(std::integral_constant<int, TR_BVH2_GLOBAL | TR_BARY>{}); break;
+        case TR_BVH4_LDS | TR_BARY: f(std::integral_constant<int, TR_BVH4_LDS | TR_BARY>{}); break;
+        case TR_BVH4_GLOBAL | TR_BARY: f(std::integral_constant<int, TR_BVH4_GLOBAL | TR_BARY>{}); break;
         default: f(std::integral_constant<int, TR_BVH2_GLOBAL>{}); break;
     }
 }
@@ -1445,10 +1464,10 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
     // traced worlds whose BVH2 sits in LDS, 8192 for marched worlds and L2-resident trees
     const bool march = (L.S.n_msph + L.S.n_mbox + L.S.n_mtor + L.S.n_msdf) != 0u;
     const uint32_t tail_at = L.tail_bounce ? L.tail_bounce
-                           : march ? kTailMarched : (tr == TR_BVH2_GLOBAL || tr == TR_BVH4_GLOBAL) ? kTailL2
+                           : march ? kTailMarched : (tr_base(tr) == TR_BVH2_GLOBAL || tr_base(tr) == TR_BVH4_GLOBAL) ? kTailL2
                            : adaptive ? OM_WF_ADAPTIVE_TAIL
                            : max_paths > (1ull << 25) ? kTailBigBatch : kTailDefault;
-    const uint32_t lanes_per_cu = (march || tr == TR_BVH2_GLOBAL || tr == TR_BVH4_GLOBAL) ? OM_WF_LANES_PER_CU_WIDE
+    const uint32_t lanes_per_cu = (march || tr_base(tr) == TR_BVH2_GLOBAL || tr_base(tr) == TR_BVH4_GLOBAL) ? OM_WF_LANES_PER_CU_WIDE
                                                                                           : OM_WF_LANES_PER_CU;
     uint32_t nseg = (uint32_t)std::min<uint64_t>((max_paths + kBlk - 1) / kBlk, (uint64_t)cus * (lanes_per_cu / kBlk));
     nseg = (nseg + kTailSpb - 1) / kTailSpb * kTailSpb;

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <exception>
 #include <mutex>
 #include <new>
 #include <string>
@@ -363,6 +364,26 @@ om_status om_world_add_cube_length(om_world* w, const float c[3], float len, con
 om_status om_world_add_triangle(om_world* w, const float o[3], const float up[3], const float vp[3], const om_material* m) {
     OM_CHECK_ADD(w && o && up && vp && valid_mat(m), "om_world_add_triangle");
     w->triangles.push_back(make_bary3(Vec3::load(o), Vec3::load(up), Vec3::load(vp), *m));
+    return OM_OK;
+}
+// n_tri x om_world_add_triangle over an indexed vertex array, all or nothing
+om_status om_world_add_triangles(om_world* w, const float* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_tri,
+                                 const om_material* m) {
+    OM_CHECK_ADD(w && valid_mat(m), "om_world_add_triangles");
+    if (n_tri == 0) return OM_OK;
+    if (!vertices || !indices) return fail(OM_ERR_INVALID, "om_world_add_triangles: null vertices or indices");
+    for (size_t k = 0; k < (size_t)n_tri * 3u; ++k)
+        if (indices[k] >= n_vertices) return fail(OM_ERR_INVALID, "om_world_add_triangles: vertex index out of range");
+    try {
+        w->triangles.reserve(w->triangles.size() + n_tri);      // the only allocation: nothing is added if it fails
+    } catch (const std::exception&) {
+        return fail(OM_ERR_NOMEM, "om_world_add_triangles: out of memory");
+    }
+    for (uint32_t k = 0; k < n_tri; ++k) {
+        const uint32_t* i = indices + 3u * (size_t)k;
+        w->triangles.push_back(make_bary3(Vec3::load(vertices + 3u * (size_t)i[0]), Vec3::load(vertices + 3u * (size_t)i[1]),
+                                          Vec3::load(vertices + 3u * (size_t)i[2]), *m));
+    }
     return OM_OK;
 }
 om_status om_world_add_parallelogram(om_world* w, const float o[3], const float up[3], const float vp[3], const om_material* m) {

@@ -43,6 +43,7 @@ struct FrozenWorld {
     std::vector<uint32_t> always;      // global indices tested outside the BVH
     std::vector<OmSkipNode> snodes;    // stackless BVH (affine prims only)
     std::vector<OmAffineTest> srecs;   // its records in leaf order
+    uint32_t n_srec_bary = 0;          // the OM_REC_BARY records among them (triangles / parallelograms in the leaves)
     std::vector<uint32_t> always2;     // prims outside the stackless BVH
     std::vector<OmAlwaysRec> always2_rec;  // the same, with their conservative boxes
     std::vector<float> srec_box;       // per srec: inflated box lo xyz, hi xyz (primary-ray tile lists)

@@ -116,6 +116,80 @@ def random_scene_api(seed=0x5EED, with_torus=False, grid_half=11, extras=True):
     return world
 
 
+# ---------------------------------------------------------------- triangle meshes
+# (vertices (V, 3) float32, faces (T, 3) uint32) pairs for HittableList.add_triangles
+
+
+def icosphere(level=2, center=(0., 0., 0.), radius=1.0):
+    """A sphere of 20 * 4**level triangles: the icosahedron, every face split in four `level` times,
+    the vertices pushed out to the sphere.  level 2: 162 vertices, 320 faces.  Outward winding."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    verts = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+             (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    verts = [np.asarray(v, dtype=np.float64) / np.linalg.norm(v) for v in verts]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+             (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10),
+             (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(level)):
+        mid = {}
+
+        def midpoint(a, b):
+            key = (a, b) if a < b else (b, a)
+            if key not in mid:
+                m = verts[a] + verts[b]
+                verts.append(m / np.linalg.norm(m))
+                mid[key] = len(verts) - 1
+            return mid[key]
+
+        split = []
+        for a, b, c in faces:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            split += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = split
+    v = np.asarray(verts, dtype=np.float64) * float(radius) + np.asarray(center, dtype=np.float64)
+    return np.ascontiguousarray(v, dtype=np.float32), np.asarray(faces, dtype=np.uint32)
+
+
+def heightfield(nx, nz, fn, extent=((0., 1.), (0., 1.))):
+    """A terrain of nx x nz cells, two triangles each: vertex (i, j) lies at x = x0 + (x1 - x0) i / nx,
+    z = z0 + (z1 - z0) j / nz, y = fn(x, z) (fn takes and returns arrays).  Upward winding."""
+    (x0, x1), (z0, z1) = extent
+    x = (x0 + (x1 - x0) * np.arange(nx + 1, dtype=np.float64) / nx).astype(np.float32)
+    z = (z0 + (z1 - z0) * np.arange(nz + 1, dtype=np.float64) / nz).astype(np.float32)
+    gx, gz = np.meshgrid(x, z, indexing="ij")
+    gy = np.asarray(fn(gx, gz), dtype=np.float32).reshape(gx.shape)
+    v = np.stack([gx, gy, gz], axis=-1).reshape(-1, 3)
+    i, j = np.meshgrid(np.arange(nx), np.arange(nz), indexing="ij")
+    a = (i * (nz + 1) + j).ravel()                       # (i, j), then (i, j+1), (i+1, j), (i+1, j+1)
+    b, c, d = a + 1, a + (nz + 1), a + (nz + 2)
+    f = np.stack([np.stack([a, b, c], axis=1), np.stack([c, b, d], axis=1)], axis=1).reshape(-1, 3)
+    return np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(f, dtype=np.uint32)
+
+
+def load_obj(path):
+    """A minimal Wavefront OBJ reader: `v x y z` and `f` lines only.  `a/b/c` corner forms are reduced
+    to the vertex index, negative indices count back from the last vertex read so far, polygons are
+    fan-triangulated (corners 0, k, k+1); every other line is ignored."""
+    verts, faces = [], []
+    with open(path, "r", encoding="utf-8", errors="replace") as fh:
+        for line in fh:
+            tok = line.split("#", 1)[0].split()
+            if not tok:
+                continue
+            if tok[0] == "v" and len(tok) >= 4:
+                verts.append([float(tok[1]), float(tok[2]), float(tok[3])])
+            elif tok[0] == "f" and len(tok) >= 4:
+                idx = []
+                for corner in tok[1:]:
+                    k = int(corner.split("/", 1)[0])
+                    k = k - 1 if k > 0 else len(verts) + k
+                    if not 0 <= k < len(verts):
+                        raise ValueError(f"{path}: face corner {corner!r} names no vertex read so far")
+                    idx.append(k)
+                faces += [(idx[0], idx[k], idx[k + 1]) for k in range(1, len(idx) - 1)]
+    return (np.asarray(verts, dtype=np.float32).reshape(-1, 3), np.asarray(faces, dtype=np.uint32).reshape(-1, 3))
+
+
 def default_camera(aspect_ratio):
     """main.rs:136-142: lookfrom (13,2,3), lookat 0, vup +y, vfov 20, aperture 0.1, focus 10."""
     return Camera.new((13., 2., 3.), (0., 0., 0.), (0., 1., 0.), 20., aspect_ratio, 0.1, 10.)
