@@ -125,6 +125,10 @@ def main():
         world = om.random_scene_api(0x5EED, with_torus=args.torus)   # main.rs:37-100 through the API
         cam = om.Camera.new((13.0, 2.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 20.0, W / H, 0.1, 10.0)  # main.rs:136-142
     frozen = world.freeze(cam)
+    if args.mesh:
+        ti = frozen.tree_info()      # which BVH2 regime the mesh landed in
+        print(f"tree: {ti['records']} records, {ti['b2_nodes']} nodes, depth {ti['b2_depth']}, regime {ti['regime']}, "
+              f"{ti['lds_bytes']} B of LDS per workgroup")
     if args.pick:
         if not (0 <= args.pick[0] < W and 0 <= args.pick[1] < H):
             ap.error("--pick: the pixel is outside the frame")

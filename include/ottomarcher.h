@@ -111,10 +111,34 @@ enum {
     OM_KERNEL_BVH2 = 5,        /* compressed BVH2 + LDS lane stack (AUTO, both pipelines): f32 nodes in LDS,
                                   or, for a tree over the LDS budget, half-precision nodes through L2
                                   behind a breadth-first LDS prefix */
-    OM_KERNEL_BVH4 = 6         /* 4-wide BVH collapsed from the BVH2, sorted near-first, LDS lane stack:
+    OM_KERNEL_BVH4 = 6,        /* 4-wide BVH collapsed from the BVH2, sorted near-first, LDS lane stack:
                                   f32 nodes in LDS, or half-precision nodes through L2 for a tree over the
                                   LDS budget (the megakernel runs OM_KERNEL_BVH2 for it) */
+    OM_KERNEL_BVH2W = 7        /* the BVH2 traversal over 32-bit child codes and a u32 LDS lane stack, half-precision
+                                  nodes through L2 behind a breadth-first LDS prefix: what AUTO, BVH2 and BVH4 run
+                                  for a tree past the 15-bit codes of OM_KERNEL_BVH2 (from ~100k triangles on);
+                                  chosen explicitly, any non-empty BVH2 runs it (wavefront and queries; the
+                                  megakernel runs OM_KERNEL_BVH for it) */
 };
+
+/* Which traversal regime a world's BVH2 gets. */
+enum {
+    OM_TREE_NONE = 0,          /* no BVH2 is walked (empty tree, or a kernel choice outside the BVH2 family) */
+    OM_TREE_LDS = 1,           /* f32 nodes staged whole in LDS */
+    OM_TREE_L2 = 2,            /* half-precision nodes through L2, 16-bit child codes */
+    OM_TREE_WIDE = 3,          /* half-precision nodes through L2, 32-bit child codes (OM_KERNEL_BVH2W) */
+    OM_TREE_FALLBACK_BVH = 4   /* the tree fits none of them: OM_KERNEL_BVH's global-memory traversal */
+};
+typedef struct om_tree_info {
+    uint32_t records;          /* leaf records in the trees (bounded spheres, cubes, triangles, parallelograms) */
+    uint32_t always_tested;    /* primitives tested for every ray, outside the trees */
+    uint32_t b2_nodes;         /* BVH2: internal nodes, */
+    uint32_t b2_leaves;        /*       leaves, */
+    uint32_t b2_depth;         /*       internal nodes on the deepest path (the lane stack's entries), */
+    uint32_t b2_max_leaf;      /*       records in the largest leaf */
+    int32_t regime;            /* OM_TREE_* */
+    uint32_t lds_bytes;        /* the wavefront's dynamic LDS per 512-lane workgroup in that regime */
+} om_tree_info;                /* 32 B */
 
 /* Work counters of the last render call (device atomics, wave-aggregated). */
 typedef struct om_counters {
@@ -222,6 +246,9 @@ om_status om_world_object_material(const om_world* w, uint32_t obj, om_material*
  * kind 0 sphere / 1 cube -> 32 floats (l2w, w2l); kind 2 triangle / 4 parallelogram -> 29 floats;
  * kind 7 torus -> 43 floats. */
 om_status om_world_export(const om_world* w, int32_t kind, uint32_t index, float* out, uint32_t out_floats);
+/* The trees a freeze of `w` builds and the regime OM_KERNEL_AUTO traces them in.  Host only: freezes
+ * and plans the world (as om_upload_world would), needs no device. */
+om_status om_world_tree_info(const om_world* w, om_tree_info* out);
 
 /* Front-end scene builders (main.rs:37-110) driven by om-rng's SplitMix64 from `seed`.
  * flags bit0: include the marched torus block (main.rs:73-81);
@@ -239,6 +266,10 @@ const char* om_last_error(const om_ctx* ctx);      /* ctx may be NULL: last glob
  * Arc<dyn Traced/Marched> user types (hits.rs:91-100) cannot cross the C-ABI. */
 om_status om_upload_world(om_ctx* ctx, const om_world* w);
 om_status om_set_kernel(om_ctx* ctx, int32_t kernel);
+/* The uploaded world's trees and the regime the wavefront and the ray queries trace them in under
+ * ctx's kernel choice (OM_TREE_NONE for a choice that walks no BVH2: brute, culled, bvh, sbvh, or a
+ * BVH4 that exists).  OM_ERR_STATE before om_upload_world. */
+om_status om_get_tree_info(om_ctx* ctx, om_tree_info* out);
 /* Host framebuffer path: `stats` is caller-owned W*H, read and written in place
  * (like PixelsBox, main.rs:192).  Includes the PCIe copies: 40 B per pixel each way per
  * call, at DMA speed when the buffer is page-locked (om_host_register), else staged by the

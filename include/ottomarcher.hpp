@@ -281,6 +281,12 @@ public:
         check(om_world_object_material(w_, obj, &m.raw));
         return m;
     }
+    // the trees a freeze builds and the regime OM_KERNEL_AUTO traces them in (host only, no device)
+    om_tree_info tree_info() const {
+        om_tree_info ti{};
+        check(om_world_tree_info(w_, &ti));
+        return ti;
+    }
 
     // hits.rs:87-89.  The camera only fed the reference's camera hash (out of scope,
     // DESIGN.md §9); the frozen world lives in HBM on `device`.
@@ -313,7 +319,13 @@ public:
     FrozenHittableList(const FrozenHittableList&) = delete;
     FrozenHittableList& operator=(const FrozenHittableList&) = delete;
 
-    void set_kernel(int32_t kernel) { check(om_set_kernel(ctx_, kernel), ctx_); }
+    void set_kernel(int32_t kernel) { check(om_set_kernel(ctx_, kernel), ctx_); }   // OM_KERNEL_* (OM_KERNEL_BVH2W included)
+    // the uploaded world's trees and the regime of this ctx's kernel choice
+    om_tree_info tree_info() const {
+        om_tree_info ti{};
+        check(om_get_tree_info(ctx_, &ti), ctx_);
+        return ti;
+    }
     void set_pipeline(int32_t pipeline) { check(om_set_pipeline(ctx_, pipeline), ctx_); }
     om_ctx* ctx() const { return ctx_; }
 

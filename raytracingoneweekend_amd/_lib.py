@@ -17,8 +17,11 @@ OM_ERR_INVALID, OM_ERR_DEVICE, OM_ERR_STATE, OM_ERR_UNSUPPORTED, OM_ERR_NOMEM = 
 OM_LAMBERTIAN, OM_METAL, OM_DIELECTRIC = 0, 1, 2
 OM_KERNEL_AUTO, OM_KERNEL_BRUTE, OM_KERNEL_CULLED, OM_KERNEL_BVH, OM_KERNEL_SBVH, OM_KERNEL_BVH2, OM_KERNEL_BVH4 = \
     0, 1, 2, 3, 4, 5, 6
+OM_KERNEL_BVH2W = 7
 KERNELS = {"auto": OM_KERNEL_AUTO, "brute": OM_KERNEL_BRUTE, "culled": OM_KERNEL_CULLED, "bvh": OM_KERNEL_BVH,
-           "sbvh": OM_KERNEL_SBVH, "bvh2": OM_KERNEL_BVH2, "bvh4": OM_KERNEL_BVH4}
+           "sbvh": OM_KERNEL_SBVH, "bvh2": OM_KERNEL_BVH2, "bvh4": OM_KERNEL_BVH4, "bvh2w": OM_KERNEL_BVH2W}
+# OM_TREE_* order: the regime of om_tree_info
+TREE_REGIMES = ("none", "lds", "l2", "wide", "fallback_bvh")
 OM_PIPELINE_MEGAKERNEL, OM_PIPELINE_WAVEFRONT, OM_PIPELINE_AUTO = 0, 1, 2
 PIPELINES = {"megakernel": OM_PIPELINE_MEGAKERNEL, "wavefront": OM_PIPELINE_WAVEFRONT, "auto": OM_PIPELINE_AUTO}
 
@@ -44,6 +47,18 @@ class om_render_params(C.Structure):
 
 class om_counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "segments", "prim_tests", "pre_tests", "march_steps", "credited")]
+
+
+class om_tree_info(C.Structure):               # 32 B
+    _fields_ = [(n, C.c_uint32) for n in ("records", "always_tested", "b2_nodes", "b2_leaves", "b2_depth", "b2_max_leaf")] + \
+               [("regime", C.c_int32), ("lds_bytes", C.c_uint32)]
+
+
+def tree_info_dict(ti):
+    """om_tree_info -> dict, the regime by name (TREE_REGIMES)"""
+    d = {n: int(getattr(ti, n)) for n, _ in om_tree_info._fields_}
+    d["regime"] = TREE_REGIMES[d["regime"]]
+    return d
 
 
 class om_ray(C.Structure):                     # ray.rs:5-8, 24 B
@@ -119,7 +134,7 @@ EXPORTS = [
     "om_multi_render_host", "om_multi_gather", "om_multi_reset", "om_rccl_library",
     "om_hit_rays_device", "om_hit_rays", "om_world_object_material", "om_query_max_grid",
     "om_occluded_rays_device", "om_occluded_rays", "om_hit_rays_windows_device", "om_hit_rays_windows",
-    "om_world_add_triangles",
+    "om_world_add_triangles", "om_world_tree_info", "om_get_tree_info",
 ]
 OM_COMM_ID_BYTES = 128
 OM_TRANSPORT_RCCL, OM_TRANSPORT_LOCAL = 0, 1
@@ -243,6 +258,8 @@ def _load():
         "om_occluded_rays": (st, [vp, C.POINTER(om_query_params), vp, vp, C.c_uint32, vp]),
         "om_hit_rays_windows_device": (st, [vp, C.POINTER(om_query_params), vp, vp, C.c_uint32, vp, vp]),
         "om_hit_rays_windows": (st, [vp, C.POINTER(om_query_params), vp, vp, C.c_uint32, vp]),
+        "om_world_tree_info": (st, [vp, C.POINTER(om_tree_info)]),
+        "om_get_tree_info": (st, [vp, C.POINTER(om_tree_info)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

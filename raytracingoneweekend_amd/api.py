@@ -332,6 +332,15 @@ class HittableList:
         check(lib.om_world_object_material(self._w, int(obj), C.byref(raw)))
         return Material(raw)
 
+    def tree_info(self):
+        """The trees a freeze of this world builds and the regime kernel "auto" traces them in
+        (om_world_tree_info: host only, no device): a dict of records, always_tested, b2_nodes,
+        b2_leaves, b2_depth, b2_max_leaf, regime ("none" / "lds" / "l2" / "wide" / "fallback_bvh")
+        and lds_bytes (the wavefront's LDS per workgroup in that regime)."""
+        ti = L.om_tree_info()
+        check(lib.om_world_tree_info(self._w, C.byref(ti)))
+        return L.tree_info_dict(ti)
+
     def freeze(self, cam=None, device=0, kernel="auto", pipeline="auto"):
         """hits.rs:87-89: snapshot to device memory (the camera is unused: the camera hash is out of scope)."""
         return FrozenHittableList(self, device=device, kernel=kernel, pipeline=pipeline)
@@ -354,6 +363,13 @@ class FrozenHittableList:
 
     def set_kernel(self, kernel):
         check(lib.om_set_kernel(self._ctx, L.KERNELS[kernel] if isinstance(kernel, str) else int(kernel)), self._ctx)
+
+    def tree_info(self):
+        """HittableList.tree_info() for the uploaded world, with the regime and LDS bytes of this
+        frozen world's own kernel choice (om_get_tree_info)."""
+        ti = L.om_tree_info()
+        check(lib.om_get_tree_info(self._ctx, C.byref(ti)), self._ctx)
+        return L.tree_info_dict(ti)
 
     def close(self):
         if getattr(self, "_ctx", None) and self._ctx.value:

@@ -452,6 +452,54 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
         for (uint32_t c : {fw.b2nodes[i].c0, fw.b2nodes[i].c1})
             if (!(c & OM_LEAF)) { depth[c] = depth[i] + 1; fw.b2_depth = std::max(fw.b2_depth, depth[c]); }
     }
+    // wide form (OmBvh2NodeW): the same tree in the same breadth-first order with
+    // 32-bit child codes and direct leaf codes, emitted straight from the builder's nodes (the 16-bit
+    // codes above collide from index 32 768 on, so nothing here reads b2nodes / b2h / b2leaves).
+    // For every world whose records fit the leaf code; om::plan_trees checks the depth.
+    fw.b2w.clear();
+    fw.b2w_depth = 0;
+    fw.b2_max_leaf = (uint32_t)max_leaf;
+    if (fw.srecs.size() < (1u << 27) && max_leaf <= 15) {
+        auto planes = [](OmBvh2NodeW& o, int k, const OmBvhNode& c) {
+            for (int i = 0; i < 3; ++i) {
+                o.b[6 * k + i] = half_out(c.lo[i], false);
+                o.b[6 * k + 3 + i] = half_out(c.hi[i], true);
+            }
+        };
+        auto leaf_code = [&](uint32_t c) { return OM_LEAFW | (leaf_first[c] << 4) | (uint32_t)b.nodes[c].right; };
+        if (b.nodes[root].left < 0) {        // a single leaf: one node, second child an empty leaf
+            OmBvh2NodeW o{};
+            OmBvhNode none{};
+            for (int i = 0; i < 3; ++i) { none.lo[i] = INFINITY; none.hi[i] = -INFINITY; }
+            planes(o, 0, b.nodes[root]);
+            planes(o, 1, none);
+            o.c0 = leaf_code(root);
+            o.c1 = OM_LEAFW;
+            fw.b2w.push_back(o);
+            fw.b2w_depth = 1;
+        } else {
+            struct QE { uint32_t node, idx, depth; };
+            std::vector<QE> q{{root, 0u, 1u}};
+            fw.b2w.push_back(OmBvh2NodeW{});
+            auto code = [&](uint32_t c, uint32_t d) {
+                if (b.nodes[c].left < 0) return leaf_code(c);
+                fw.b2w.push_back(OmBvh2NodeW{});
+                q.push_back({c, (uint32_t)(fw.b2w.size() - 1), d});
+                return (uint32_t)(fw.b2w.size() - 1);
+            };
+            for (size_t h = 0; h < q.size(); ++h) {
+                const QE e = q[h];
+                const OmBvhNode& src = b.nodes[e.node];
+                OmBvh2NodeW o{};
+                planes(o, 0, b.nodes[(uint32_t)src.left]);
+                planes(o, 1, b.nodes[(uint32_t)src.right]);
+                o.c0 = code((uint32_t)src.left, e.depth + 1u);
+                o.c1 = code((uint32_t)src.right, e.depth + 1u);
+                fw.b2w[e.idx] = o;
+                fw.b2w_depth = std::max(fw.b2w_depth, e.depth);
+            }
+        }
+    }
     // conservative world box of every leaf record (the tree's own item boxes)
     fw.srec_box.clear();
     for (const OmAffineTest& t : fw.srecs) {

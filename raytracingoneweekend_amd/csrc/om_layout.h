@@ -184,6 +184,20 @@ struct OM_ALIGN16 OmBvh2NodeH {
     uint16_t c0, c1;
     uint32_t pad;
 };
+// The wide form of the half node (32 B; trees past the 15-bit codes): the same
+// planes, rounded outward by the same half_out, and 32-bit child codes in place of c0, c1, pad.
+// A code below OM_LEAFW is a node index; otherwise the child is a leaf, in the direct form
+// OM_LEAFW | first_record << 4 | count (count <= 15, first < 2^27: no leaf table).  Emitted
+// breadth-first like b2h, for every world with a BVH2; the traversal stack holds the 32-bit codes.
+#define OM_LEAFW 0x80000000u
+struct OM_ALIGN16 OmBvh2NodeW {
+    uint16_t b[12];
+    uint32_t c0, c1;
+};
+// lane-stack bound of the wide regime: 32 u32 entries for 512 lanes are 64 KiB, which
+// of a gfx950 CU's 160 KiB still leaves two workgroups per CU; the builder's depth bound (kSahDepth + log2 n)
+// reaches 32 only past 2^22 records
+constexpr uint32_t kB2WideStack = 32u;
 // f32 BVH2 nodes + leaf table of at most this many bytes (nodes counted at their 64 B in memory)
 // are staged whole in LDS per workgroup; a bigger tree is read through L2 (half nodes, an LDS
 // prefix) and built with smaller leaves.  The wavefront stages the nodes OM_B2_NODE_STRIDE (80) B
@@ -210,9 +224,12 @@ struct OmSceneDev {
     uint32_t n_sph, n_cube, n_tri, n_plane, n_para, n_msph, n_mbox, n_mtor, n_msdf;
     uint32_t n_bvh_nodes;
     uint32_t n_always;            // number of unbounded/huge prims tested outside the BVH
+    uint32_t n_b2wnodes;          // wide BVH2 (32-bit child codes): its nodes, OmBvh2NodeW, behind the
+                                  // n_b2nodes half nodes in b2h's buffer; 0: not usable (om::plan_trees)
     const uint32_t* always;       // their global indices (ascending)
     // type offsets of the global index space
     uint32_t off_cube, off_tri, off_plane, off_para, off_msph, off_mbox, off_mtor, off_msdf, n_total;
+    uint32_t b2w_stack;           // u32 lane-stack entries the wide BVH2 needs (its internal depth, <= kB2WideStack)
     // stackless BVH over the affine primitives, and the barycentric ones of worlds with at least
     // OM_BARY_TREE_MIN of them (records carry gi | OM_REC_CUBE / OM_REC_BARY in `pad`)
     const OmSkipNode* snodes; const OmAffineTest* srecs; const uint32_t* always2;
@@ -236,6 +253,10 @@ struct OmSceneDev {
     uint32_t b4_stack;            // lane-stack entries: 3 per level + 3 for the unconditional pushes
     uint32_t n_srec_bary;         // OM_REC_BARY records in srecs (0: the traversals run without the barycentric leaf test)
 };
+// (n_b2wnodes and b2w_stack sit where the struct had padding and the wide nodes share b2h's buffer,
+// so the kernel argument keeps its size and every other field its offset: a longer argument
+// moved the megakernel's SBVH kernels from 69-78 to 75-81 VGPRs)
+static_assert(sizeof(OmSceneDev) == 368, "OmSceneDev is a kernel argument: its size and offsets are part of every kernel's register budget");
 
 struct OmCamDev {
     float origin[3], horizontal[3], vertical[3], llc_minus_origin[3];

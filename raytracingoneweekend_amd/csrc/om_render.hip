@@ -11,6 +11,9 @@
 // benefit of wavefront compaction without the HBM ray queues.  A wave owns an
 // 8x8 pixel tile for ray coherence.  Scene records are read at wave-uniform
 // addresses (scalar loads) and stay L2/LDS resident.
+//
+// The wide BVH2 (32-bit child codes) is the wavefront's and the ray queries':
+// the megakernel keeps MODE_BVH for a tree past the 15-bit codes and for OM_KERNEL_BVH2W.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +40,7 @@ static_assert(sizeof(om_ray) == 24 && sizeof(om_hit) == 32 && sizeof(om_query_pa
 static_assert(sizeof(om_ray_window) == 8, "query window layout");
 static_assert(OM_QUERY_BLOCK == 512, "OM_QUERY_BLOCK is the wavefront workgroup size");
 static_assert(sizeof(OmAffineTest) == 64 && sizeof(OmBvhNode) == 32, "layout");
+static_assert(sizeof(OmBvh2NodeW) == sizeof(OmBvh2NodeH) && sizeof(om_tree_info) == 32, "wide node / om_tree_info layout");
 
 namespace {
 
@@ -264,6 +268,7 @@ struct om_ctx {
     std::vector<DevBuf> scene_bufs;
     OmSceneDev scene{};
     bool have_world = false;
+    om_tree_info tree_info{};           // the uploaded world's trees (om_get_tree_info)
     int kernel = OM_KERNEL_AUTO;
     DevBuf counters, stats, pixels, view_scratch, view_rgb;
     // jitter tables, one immutable device buffer per (seed, spp_total): a table that queued
@@ -463,7 +468,7 @@ om_status ensure_tile_lists(om_ctx* c, const om_camera* cam, uint32_t W, uint32_
 int wf_trace_mode(int mode) {
     return mode == OM_KERNEL_BRUTE ? MODE_BRUTE : mode == OM_KERNEL_CULLED ? MODE_CULLED
          : mode == OM_KERNEL_BVH ? MODE_BVH : mode == OM_KERNEL_BVH2 ? 6
-         : mode == OM_KERNEL_BVH4 ? 8 : MODE_SBVH_LDS;
+         : mode == OM_KERNEL_BVH4 ? 8 : mode == OM_KERNEL_BVH2W ? 10 : MODE_SBVH_LDS;
 }
 
 om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_pixel_stats* dev_stats,
@@ -529,7 +534,9 @@ om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_
         L.timer = &c->timer;
         L.tile_off = nullptr; L.tile_idx = nullptr; L.tile_tnear = nullptr;
         L.progress_host = c->progress_host;
-        if (mode == OM_KERNEL_BVH2 && c->scene.n_b2nodes) {
+        // (a tree past the 15-bit codes has n_b2nodes 0: its primary rays traverse, and om_tiles.cpp
+        // lists at most 65 535 records anyway; OM_KERNEL_BVH2W takes the lists like OM_KERNEL_BVH2)
+        if ((mode == OM_KERNEL_BVH2 && c->scene.n_b2nodes) || (mode == OM_KERNEL_BVH2W && c->scene.n_b2wnodes)) {
             if ((s = ensure_tile_lists(c, cam, p->width, p->height, stream)) != OM_OK) return s;
             if (c->tiles_use) {
                 L.tile_off = (const uint32_t*)c->tile_off.p; L.tile_idx = (const uint16_t*)c->tile_idx.p;
@@ -647,8 +654,24 @@ om_status om_upload_world(om_ctx* c, const om_world* w) {
     UP(tri, tri); UP(plane, plane); UP(para, para);
     UP(msph, msph); UP(mbox, mbox); UP(mtor, mtor); UP(msdf, msdf); UP(msdf_ops, msdf_ops);
     UP(mats, mats); UP(bloom, bloom); UP(bvh, bvh); UP(bvh_prims, bvh_prims); UP(always, always);
-    UP(snodes, snodes); UP(srecs, srecs); UP(always2, always2); UP(always2_rec, always2_rec); UP(b2nodes, b2nodes); UP(b2h, b2h); UP(b2leaves, b2leaves);
+    UP(snodes, snodes); UP(srecs, srecs); UP(always2, always2); UP(always2_rec, always2_rec); UP(b2nodes, b2nodes); UP(b2leaves, b2leaves);
 #undef UP
+    // which trees are usable and which are staged in LDS: om::plan_trees (om_world.h)
+    const om::TreePlan plan = om::plan_trees(fw);
+    // one buffer behind S.b2h: the half nodes of a tree within the 15-bit codes, then the wide nodes
+    // (OmBvh2NodeW, same size) of a tree the wide regime can run, which the kernels find at
+    // b2h + n_b2nodes -- OmSceneDev keeps its size (om_layout.h)
+    {
+        static_assert(sizeof(OmBvh2NodeW) == sizeof(OmBvh2NodeH), "wide and half nodes share a buffer");
+        std::vector<OmBvh2NodeH> both;
+        if (plan.b2_ok) both = fw.b2h;
+        if (plan.b2w_ok) {
+            const size_t at = both.size();
+            both.resize(at + fw.b2w.size());
+            std::memcpy(both.data() + at, fw.b2w.data(), fw.b2w.size() * sizeof(OmBvh2NodeW));
+        }
+        if ((s = upload(c, both, &S.b2h)) != OM_OK) return s;
+    }
     c->srec_box = fw.srec_box;
     c->world_gen++;
     c->tiles_valid = false;
@@ -660,8 +683,6 @@ om_status om_upload_world(om_ctx* c, const om_world* w) {
     S.n_bvh_nodes = (uint32_t)fw.bvh.size();
     S.n_always = (uint32_t)fw.always.size();
     S.n_snodes = (uint32_t)fw.snodes.size(); S.n_srecs = (uint32_t)fw.srecs.size(); S.n_always2 = (uint32_t)fw.always2.size();
-    // which trees are usable and which are staged in LDS: om::plan_trees (om_world.h)
-    const om::TreePlan plan = om::plan_trees(fw);
     S.lds_bytes = plan.lds_bytes;
     S.n_b2nodes = plan.n_b2nodes; S.n_b2leaves = plan.n_b2leaves;
     S.b2_direct = plan.b2_direct; S.b2_stack = plan.b2_stack; S.b2_lds_bytes = plan.b2_lds_bytes;
@@ -669,6 +690,8 @@ om_status om_upload_world(om_ctx* c, const om_world* w) {
     if (plan.b4_ok && (s = upload(c, fw.b4h, &S.b4h)) != OM_OK) return s;
     S.n_b4nodes = plan.b4_ok ? (uint32_t)fw.b4nodes.size() : 0u;
     S.b4_stack = plan.b4_stack; S.b4_lds_bytes = plan.b4_lds_bytes;
+    S.n_b2wnodes = plan.n_b2wnodes; S.b2w_stack = plan.b2w_stack;
+    om::fill_tree_info(fw, plan, &c->tree_info);
     // barycentric leaf records carry gi in 30 bits beside the two kind bits (om_layout.h OM_REC_GI)
     S.n_srec_bary = fw.n_srec_bary;
     if (fw.n_srec_bary && fw.offsets[om::K_N] > OM_REC_GI)
@@ -680,8 +703,19 @@ om_status om_upload_world(om_ctx* c, const om_world* w) {
 
 om_status om_set_kernel(om_ctx* c, int32_t k) {
     if (!c) return set_err(nullptr, OM_ERR_INVALID, "null ctx");
-    if (k < OM_KERNEL_AUTO || k > OM_KERNEL_BVH4) return set_err(c, OM_ERR_INVALID, "om_set_kernel: unknown kernel");
+    if (k < OM_KERNEL_AUTO || k > OM_KERNEL_BVH2W) return set_err(c, OM_ERR_INVALID, "om_set_kernel: unknown kernel");
     c->kernel = k;
+    return OM_OK;
+}
+
+om_status om_get_tree_info(om_ctx* c, om_tree_info* out) {
+    if (!c) return set_err(nullptr, OM_ERR_INVALID, "om_get_tree_info: null ctx");
+    if (!out) return set_err(c, OM_ERR_INVALID, "om_get_tree_info: null out");
+    if (!c->have_world) return set_err(c, OM_ERR_STATE, "om_upload_world must precede om_get_tree_info");
+    *out = c->tree_info;
+    int mode = c->kernel;
+    if (mode == OM_KERNEL_AUTO) mode = OM_KERNEL_BVH2;
+    omw::tree_regime(wf_trace_mode(mode), c->scene, &out->regime, &out->lds_bytes);
     return OM_OK;
 }
 

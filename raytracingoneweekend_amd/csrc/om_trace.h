@@ -16,6 +16,11 @@ template <int K> __device__ __forceinline__ float b2p(const OmBvh2Node& N) {
 // A half-precision box plane (OmBvh2NodeH) as f32, exactly.
 __device__ __forceinline__ float h2f(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
 template <int K> __device__ __forceinline__ float b2p(const OmBvh2NodeH& N) { return h2f(N.b[K]); }
+template <int K> __device__ __forceinline__ float b2p(const OmBvh2NodeW& N) { return h2f(N.b[K]); }
+// Child codes of a BVH2 node type: the leaf bit and the lane-stack entry that holds a code
+// (16-bit codes, OM_LEAF; OmBvh2NodeW: 32-bit codes, OM_LEAFW).
+template <class Node> struct B2Codes { static constexpr uint32_t LEAF = OM_LEAF; typedef uint16_t stk_t; };
+template <> struct B2Codes<OmBvh2NodeW> { static constexpr uint32_t LEAF = OM_LEAFW; typedef uint32_t stk_t; };
 // Plane P (lox loy loz hix hiy hiz) of child k of a 4-wide node, f32 or half.
 template <int P> __device__ __forceinline__ float b4p(const OmBvh4Node& N, int k) {
     return P == 0 ? N.lox[k] : P == 1 ? N.loy[k] : P == 2 ? N.loz[k] : P == 3 ? N.hix[k] : P == 4 ? N.hiy[k] : N.hiz[k];
@@ -301,6 +306,18 @@ __device__ __forceinline__ void test_leaf(const OmSceneDev& S, const OmAffineTes
     for (uint32_t k = 0; k < cnt; ++k) {
         test_rec(S, recs[first + k], o, d, tmin, closest, best, w);
         if (Wk::ANY && best >= 0) return;
+    }
+}
+// The leaf of child code `code` of a node of type Node: a 16-bit code through leaf_payload, a wide
+// code (OM_LEAFW | first << 4 | count, first < 2^27) unpacked to the same (first << 8) | count.
+template <class Node, class Wk>
+__device__ __forceinline__ void test_leaf_code(const OmSceneDev& S, const OmAffineTest* recs, const uint32_t* leaves, uint32_t code,
+                                               F3 o, F3 d, float tmin, float& closest, int& best, Wk& w) {
+    if constexpr (B2Codes<Node>::LEAF == OM_LEAFW) {
+        // first < 2^27 does not fit test_leaf's 24 bits: the record pointer moves instead
+        test_leaf(S, recs + ((code & ~OM_LEAFW) >> 4), code & 15u, o, d, tmin, closest, best, w);
+    } else {
+        test_leaf(S, recs, leaf_payload(S, code, leaves), o, d, tmin, closest, best, w);
     }
 }
 
@@ -736,9 +753,12 @@ __device__ __forceinline__ int traced_tiles(const OmSceneDev& S, const uint32_t*
 // occupancy on C3: DESIGN.md §8, r06.)
 template <int DEPTH, int STRIDE, class Wk, bool HYB = false, class Node = OmBvh2Node, int CUNIT = (int)sizeof(Node)>
 __device__ __forceinline__ int traced_bvh2(const OmSceneDev& S, const Node* nodes, const uint32_t* leaves,
-                                           const OmAffineTest* recs, uint16_t* stk,
+                                           const OmAffineTest* recs, typename B2Codes<Node>::stk_t* stk,
                                            F3 o, F3 d, float tmin, float& closest, Wk& w,
                                            const Node* gnodes = nullptr, uint32_t nl = 0) {
+    // (OmBvh2NodeW: the same loop over 32-bit codes and u32 stack entries)
+    constexpr uint32_t kLeaf = B2Codes<Node>::LEAF;
+    typedef typename B2Codes<Node>::stk_t stk_t;
     if (!isfinite(o.x + o.y + o.z + d.x + d.y + d.z)) return nonfinite_hit(S, closest);
     int best = -1;
     const float ix = inv_dir(d.x);
@@ -779,8 +799,8 @@ __device__ __forceinline__ int traced_bvh2(const OmSceneDev& S, const Node* node
     // leaf, then the wave's leaves are tested) -- written as one flat if/else loop instead,
     // C1 ran 14% slower (r04)
     for (;;) {
-        if (cur >= OM_LEAF) {                       // the single leaf site (16-bit codes: one compare, no and)
-            test_leaf(S, recs, leaf_payload(S, cur, leaves), o, d, tmin, closest, best, w);
+        if (cur >= kLeaf) {                         // the single leaf site (one compare, no and)
+            test_leaf_code<Node>(S, recs, leaves, cur, o, d, tmin, closest, best, w);
             if (Wk::ANY && best >= 0) break;
             if (!pop()) break;
             continue;
@@ -789,7 +809,7 @@ __device__ __forceinline__ int traced_bvh2(const OmSceneDev& S, const Node* node
         bool h0, h1, swap;
         slabs(N, h0, h1, swap);
         if (h0 && h1) {                             // near child next, far child pushed
-            stk[sp * STRIDE] = (uint16_t)(swap ? N.c0 : N.c1);   // sp < depth: om_upload_world sizes the stack
+            stk[sp * STRIDE] = (stk_t)(swap ? N.c0 : N.c1);      // sp < depth: om_upload_world sizes the stack
             ++sp;
             cur = swap ? N.c1 : N.c0;
         } else if (h0 || h1) {

@@ -45,6 +45,14 @@
 #ifndef OM_WF_HYB_BYTES
 #define OM_WF_HYB_BYTES 16384
 #endif
+// The same for the wide BVH2 (32-bit child codes behind a u32 lane stack), whose
+// stack alone takes 2 KiB per level: 0, every node through L2.  Measured (MI355X, one session, tools/
+// mesh_bench.py --heightfield 512: C1's world + 524 288 triangles, depth 20 = 40 KiB of stack), 0 / 8 / 16
+// KiB -> render 50.4 / 53.8 / 70.5-72.9 ms, shuffled closest hit 1.169 / 1.505 / 1.724 ms, secondary
+// closest hit 1.017 / 1.005 / 1.420 ms (profiles/mesh/large_mesh_bench.json).
+#ifndef OM_WF_HYBW_BYTES
+#define OM_WF_HYBW_BYTES 0
+#endif
 // The same for the half-precision 4-wide tree (OM_KERNEL_BVH4 on a tree too big for LDS, §5.7).
 // C3 (r05_b4h): 0 / 4 / 8 / 12 KB -> 4028 / 3943 / 3895-3918 / 3918 Msamples/s: lanes whose node
 // is in LDS and lanes whose node is not run both loads, so every node comes through L1/L2.

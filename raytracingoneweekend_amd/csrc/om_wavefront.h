@@ -115,5 +115,9 @@ struct Query {
 // Traces Q.n rays in one persistent launch on `stream` (at most query_max_grid() workgroups).
 hipError_t query(const Query& Q, hipStream_t stream);
 uint32_t query_max_grid();       // on the current device
+// What renders and queries with this trace_mode run on scene S (om_get_tree_info): the BVH2 regime
+// as an OM_TREE_* value (OM_TREE_NONE: a variant that walks no BVH2) and the dynamic LDS bytes a
+// workgroup requests for it.
+void tree_regime(int trace_mode, const OmSceneDev& S, int32_t* regime, uint32_t* lds_bytes);
 
 }  // namespace omw

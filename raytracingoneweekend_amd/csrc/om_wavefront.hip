@@ -62,6 +62,10 @@ namespace {
 constexpr uint32_t kNoSample = 0xFFFFFFFFu;
 enum { TR_BRUTE = 1, TR_CULLED = 2, TR_BVH = 3, TR_SBVH_LDS = 4, TR_SBVH_GLOBAL = 5, TR_BVH2_LDS = 6, TR_BVH2_GLOBAL = 7,
        TR_BVH4_LDS = 8, TR_BVH4_GLOBAL = 9,
+       // the BVH2 with 32-bit child codes and a u32 lane stack (OmBvh2NodeW): trees past
+       // the 15-bit codes, and any non-empty BVH2 under OM_KERNEL_BVH2W.  Always with TR_BARY: one set
+       // of instantiations, whose leaf test handles sphere and cube records by tag
+       TR_BVH2_WIDE = 10,
        // flag on a tree variant (TR_SBVH_GLOBAL, TR_BVH2_*, TR_BVH4_*): the world's leaves hold triangles /
        // parallelograms (OmSceneDev::n_srec_bary), so the kernels are the instantiations
        // whose leaf test carries the barycentric case (WorkT's BARY); every other world runs the
@@ -82,6 +86,7 @@ static_assert(kB2LdsBudget / sizeof(OmBvh2Node) * (kB2Stride / 16u) < OM_LEAF, "
 // S-traced: 9 KiB per 512-lane workgroup instead of 24 KiB at the 24-entry bound).
 template <int TR>
 __host__ __device__ inline uint32_t stack_bytes(const OmSceneDev& S) {
+    if (tr_base(TR) == TR_BVH2_WIDE) return kBlk * S.b2w_stack * 4u;          // u32 entries
     return kBlk * ((tr_base(TR) == TR_BVH4_LDS || tr_base(TR) == TR_BVH4_GLOBAL) ? S.b4_stack : S.b2_stack) * 2u;
 }
 // LDS bytes of a BVH2 staged whole (TR_BVH2_LDS): padded nodes + leaf table
@@ -112,6 +117,14 @@ constexpr uint32_t kTailBigBatch = 24;
 __host__ __device__ inline uint32_t hyb_nodes(const OmSceneDev& S) {
     constexpr uint32_t kCap = OM_WF_HYB_BYTES / (uint32_t)sizeof(OmBvh2NodeH);
     return S.b2_lds_bytes ? 0u : (S.n_b2nodes < kCap ? S.n_b2nodes : kCap);
+}
+// the wide BVH2's nodes: behind the n_b2nodes half nodes of b2h's buffer (om_layout.h, om_upload_world)
+static_assert(sizeof(OmBvh2NodeW) == sizeof(OmBvh2NodeH), "wide and half nodes share a buffer");
+__host__ __device__ inline const OmBvh2NodeW* wide_nodes(const OmSceneDev& S) { return (const OmBvh2NodeW*)(S.b2h + S.n_b2nodes); }
+// the wide BVH2's breadth-first prefix in LDS (om_tuning.h OM_WF_HYBW_BYTES)
+__host__ __device__ inline uint32_t hybw_nodes(const OmSceneDev& S) {
+    constexpr uint32_t kCap = OM_WF_HYBW_BYTES / (uint32_t)sizeof(OmBvh2NodeW);
+    return S.n_b2wnodes < kCap ? S.n_b2wnodes : kCap;
 }
 __host__ __device__ inline uint32_t hyb4_nodes(const OmSceneDev& S) {
     constexpr uint32_t kCap = OM_WF_HYB4_BYTES / (uint32_t)sizeof(OmBvh4NodeH);
@@ -248,6 +261,9 @@ struct Tracer {
     const OmBvh2NodeH* h2l;  // TR_BVH2_GLOBAL: half nodes [0, nl) staged in LDS
     const OmBvh2NodeH* h2g;  //                 every half node, through L2
     uint32_t nl;
+    const OmBvh2NodeW* w2l;  // TR_BVH2_WIDE: wide nodes [0, nl) staged in LDS
+    const OmBvh2NodeW* w2g;  //               every wide node, through L2
+    uint32_t* stk32;         //               its u32 lane stack
     const OmBvh4Node* b4n;
     const OmBvh4NodeH* h4l;  // TR_BVH4_GLOBAL: half nodes [0, nl) staged in LDS
     const OmBvh4NodeH* h4g;  //                 every half node, through L2
@@ -264,6 +280,7 @@ __device__ __forceinline__ Tracer stage_scene(const OmSceneDev& S) {   // every 
     t.b2n = S.b2nodes; t.b4n = S.b4nodes; t.bl = S.b2leaves; t.recs = S.srecs;
     t.h2l = S.b2h; t.h2g = S.b2h; t.nl = 0;
     t.h4l = S.b4h; t.h4g = S.b4h;
+    t.w2l = wide_nodes(S); t.w2g = wide_nodes(S); t.stk32 = (uint32_t*)wf_lds + threadIdx.x;
     if (TR == TR_BVH4_GLOBAL && hyb4_nodes(S)) {
         t.nl = hyb4_nodes(S);
         uint4* dst = wf_lds + STACKS * stack_bytes<TR>(S) / 16u;
@@ -271,6 +288,14 @@ __device__ __forceinline__ Tracer stage_scene(const OmSceneDev& S) {   // every 
         for (uint32_t i = threadIdx.x; i < t.nl * (uint32_t)(sizeof(OmBvh4NodeH) / 16u); i += kBlk) dst[i] = sn[i];
         __syncthreads();
         t.h4l = (const OmBvh4NodeH*)dst;
+    }
+    if (TR == TR_BVH2_WIDE && hybw_nodes(S)) {
+        t.nl = hybw_nodes(S);
+        uint4* dst = wf_lds + STACKS * stack_bytes<TR>(S) / 16u;
+        const uint4* sn = (const uint4*)wide_nodes(S);
+        for (uint32_t i = threadIdx.x; i < t.nl * (uint32_t)(sizeof(OmBvh2NodeW) / 16u); i += kBlk) dst[i] = sn[i];
+        __syncthreads();
+        t.w2l = (const OmBvh2NodeW*)dst;
     }
     if (TR == TR_BVH2_GLOBAL && hyb_nodes(S)) {
         t.nl = hyb_nodes(S);
@@ -318,6 +343,8 @@ __device__ __forceinline__ int trace_traced(const OmSceneDev& S, const Tracer& T
         return traced_bvh2<kStackDepth, kBlk, Wk, false, OmBvh2Node, 16>(S, T.b2n, T.bl, T.recs, T.stk, o, d, tmin, closest, w);
     if (TR == TR_BVH2_GLOBAL)
         return traced_bvh2<kStackDepth, kBlk, Wk, true>(S, T.h2l, T.bl, T.recs, T.stk, o, d, tmin, closest, w, T.h2g, T.nl);
+    if (TR == TR_BVH2_WIDE)
+        return traced_bvh2<(int)kB2WideStack, kBlk, Wk, true>(S, T.w2l, T.bl, T.recs, T.stk32, o, d, tmin, closest, w, T.w2g, T.nl);
     if (TR == TR_SBVH_GLOBAL) return traced_sbvh(S, S.snodes, S.srecs, o, d, tmin, closest, w);
     if (TR == TR_BVH) return traced_bvh(S, o, d, tmin, closest, w);
     return traced_brute<TR == TR_CULLED>(S, o, d, tmin, closest, w);
@@ -480,7 +507,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
                 if (HIT) {
                     const float2 h = hitbuf[i];
                     closest = h.x; best = __float_as_int(h.y);
-                } else if (FIRST && (tr_base(TR) == TR_BVH2_LDS || tr_base(TR) == TR_BVH2_GLOBAL) && R.tile_off) {
+                } else if (FIRST && (tr_base(TR) == TR_BVH2_LDS || tr_base(TR) == TR_BVH2_GLOBAL || tr_base(TR) == TR_BVH2_WIDE) && R.tile_off) {
                     const uint32_t line = p_pixel / P.width;
                     const uint32_t tile = (p_pixel - line * P.width) / 8u + (line / 8u) * P.tiles_x;
                     closest = P.tmax;
@@ -963,7 +990,7 @@ __device__ __forceinline__ void query_rays(const OmSceneDev& S, const OmParamsDe
         // infinite root is rejected where a NaN root is accepted).  A query can be handed any ray,
         // so such rays (never a whole wave in practice) run the reference loop itself.
         constexpr int T0 = tr_base(TR);
-        constexpr bool kShortcut = T0 == TR_BVH2_LDS || T0 == TR_BVH2_GLOBAL || T0 == TR_BVH4_LDS || T0 == TR_BVH4_GLOBAL;
+        constexpr bool kShortcut = T0 == TR_BVH2_LDS || T0 == TR_BVH2_GLOBAL || T0 == TR_BVH4_LDS || T0 == TR_BVH4_GLOBAL || T0 == TR_BVH2_WIDE;
         float tmin = P.tmin, tmax = P.tmax;
         if (WIN) load_query_window(windows, i, tmin, tmax);
         if ((kShortcut && !isfinite(o.x + o.y + o.z + d.x + d.y + d.z)) || (WIN && window_edge(tmin, tmax))) {
@@ -1331,10 +1358,19 @@ hipError_t ensure_events(Buffers& B, size_t n) {
 // world: renders and ray queries share it.
 int pick_trace(int trace_mode, const OmSceneDev& S) {
     int tr = trace_mode == TR_SBVH_LDS ? TR_SBVH_GLOBAL : trace_mode;
+    // OM_KERNEL_BVH2W: the wide variant for any world that has the wide nodes; an empty tree takes
+    // OM_KERNEL_BVH2's fallbacks below
+    if (tr == TR_BVH2_WIDE) {
+        if (S.n_b2wnodes) return TR_BVH2_WIDE | TR_BARY;
+        tr = TR_BVH2_LDS;
+    }
     if (tr == TR_BVH4_LDS) tr = S.n_b4nodes == 0 ? TR_BVH2_LDS : (S.b4_lds_bytes ? TR_BVH4_LDS : TR_BVH4_GLOBAL);
     // an empty BVH2 (no bounded sphere/cube: marched-only worlds, C2) takes the reference loop
     // when the old BVH holds at most one leaf: TR_BVH's 64-entry stack lives in scratch memory,
     // which every k_march / k_tail wave would then carry for nothing (C2: 1785 vs 1649, r02_v8)
+    // a tree past the 15-bit codes (n_b2nodes == 0) with the wide nodes usable: the same traversal
+    // over 32-bit codes instead of TR_BVH; BVH4 requests arrive here too
+    if (tr == TR_BVH2_LDS && S.n_b2nodes == 0 && S.n_b2wnodes) return TR_BVH2_WIDE | TR_BARY;
     if (tr == TR_BVH2_LDS)
         tr = S.n_b2nodes == 0 ? (S.n_bvh_nodes <= 1u ? TR_BRUTE : TR_BVH) : (S.b2_lds_bytes ? TR_BVH2_LDS : TR_BVH2_GLOBAL);
     // triangles / parallelograms in the leaves: the tree variants' TR_BARY instantiations
@@ -1352,6 +1388,7 @@ uint32_t trace_lds(int trf, const OmSceneDev& S) {
          : tr == TR_BVH2_GLOBAL ? stack_bytes<TR_BVH2_GLOBAL>(S) + hyb_nodes(S) * (uint32_t)sizeof(OmBvh2NodeH)
          : tr == TR_BVH4_LDS ? stack_bytes<TR_BVH4_LDS>(S) + S.b4_lds_bytes
          : tr == TR_BVH4_GLOBAL ? stack_bytes<TR_BVH4_GLOBAL>(S) + hyb4_nodes(S) * (uint32_t)sizeof(OmBvh4NodeH)
+         : tr == TR_BVH2_WIDE ? stack_bytes<TR_BVH2_WIDE>(S) + hybw_nodes(S) * (uint32_t)sizeof(OmBvh2NodeW)
          : 0u;
 }
 // f(std::integral_constant<int, TR>) for a variant pick_trace returned
@@ -1370,6 +1407,7 @@ void with_tr(int tr, F f) {
         case TR_BVH2_GLOBAL | TR_BARY: f(std::integral_constant<int, TR_BVH2_GLOBAL | TR_BARY>{}); break;
         case TR_BVH4_LDS | TR_BARY: f(std::integral_constant<int, TR_BVH4_LDS | TR_BARY>{}); break;
         case TR_BVH4_GLOBAL | TR_BARY: f(std::integral_constant<int, TR_BVH4_GLOBAL | TR_BARY>{}); break;
+        case TR_BVH2_WIDE | TR_BARY: f(std::integral_constant<int, TR_BVH2_WIDE | TR_BARY>{}); break;
         default: f(std::integral_constant<int, TR_BVH2_GLOBAL>{}); break;
     }
 }
@@ -1463,12 +1501,13 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
     // segments, a multiple of the tail grouping: 4096 lanes per CU (8 workgroups of 512) for
     // traced worlds whose BVH2 sits in LDS, 8192 for marched worlds and L2-resident trees
     const bool march = (L.S.n_msph + L.S.n_mbox + L.S.n_mtor + L.S.n_msdf) != 0u;
+    // trees read through L2 (the wide BVH2 among them)
+    const bool l2_tree = tr_base(tr) == TR_BVH2_GLOBAL || tr_base(tr) == TR_BVH4_GLOBAL || tr_base(tr) == TR_BVH2_WIDE;
     const uint32_t tail_at = L.tail_bounce ? L.tail_bounce
-                           : march ? kTailMarched : (tr_base(tr) == TR_BVH2_GLOBAL || tr_base(tr) == TR_BVH4_GLOBAL) ? kTailL2
+                           : march ? kTailMarched : l2_tree ? kTailL2
                            : adaptive ? OM_WF_ADAPTIVE_TAIL
                            : max_paths > (1ull << 25) ? kTailBigBatch : kTailDefault;
-    const uint32_t lanes_per_cu = (march || tr_base(tr) == TR_BVH2_GLOBAL || tr_base(tr) == TR_BVH4_GLOBAL) ? OM_WF_LANES_PER_CU_WIDE
-                                                                                          : OM_WF_LANES_PER_CU;
+    const uint32_t lanes_per_cu = (march || l2_tree) ? OM_WF_LANES_PER_CU_WIDE : OM_WF_LANES_PER_CU;
     uint32_t nseg = (uint32_t)std::min<uint64_t>((max_paths + kBlk - 1) / kBlk, (uint64_t)cus * (lanes_per_cu / kBlk));
     nseg = (nseg + kTailSpb - 1) / kTailSpb * kTailSpb;
     const uint32_t segcap = seg_capacity(max_paths, nseg);
@@ -1482,6 +1521,11 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
     (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
     if (!march && tail_at < depth_cap && tail_lds(lds, nseg) > (uint32_t)lds_max) {
         err = "the tail's LDS request exceeds the device's limit";
+        return hipErrorInvalidValue;
+    }
+    // every other launch of the variant requests `lds` (a wide tree at the 32-entry bound: 64 KiB of stack)
+    if (lds > (uint32_t)lds_max) {
+        err = "the traversal's LDS request exceeds the device's limit";
         return hipErrorInvalidValue;
     }
     Gen R;
@@ -1595,12 +1639,28 @@ uint32_t query_max_grid() {
     return (uint32_t)cus * (uint32_t)(OM_WF_WAVES * 4 * 64 / kBlk);
 }
 
+void tree_regime(int trace_mode, const OmSceneDev& S, int32_t* regime, uint32_t* lds_bytes) {
+    const int tr = pick_trace(trace_mode, S);
+    const int b = tr_base(tr);
+    // TR_BVH counts as the fallback only where a BVH2-family choice fell back to it
+    const bool asked_b2 = trace_mode == TR_BVH2_LDS || trace_mode == TR_BVH4_LDS || trace_mode == TR_BVH2_WIDE;
+    *regime = b == TR_BVH2_LDS ? OM_TREE_LDS : b == TR_BVH2_GLOBAL ? OM_TREE_L2 : b == TR_BVH2_WIDE ? OM_TREE_WIDE
+            : (b == TR_BVH && asked_b2) ? OM_TREE_FALLBACK_BVH : OM_TREE_NONE;
+    *lds_bytes = trace_lds(tr, S);
+}
+
 // One k_query (Q.hits) or k_occluded (Q.occluded) launch on `st`: the variant renders would trace
 // with (pick_trace), MARCH / USER from the world's marched and SDF-program counts.
 hipError_t query(const Query& Q, hipStream_t st) {
     if (Q.n == 0) return hipSuccess;
     const int tr = pick_trace(Q.trace_mode, Q.S);
     const uint32_t lds = trace_lds(tr, Q.S);
+    {   // refused here, not as a launch error (a wide tree at the 32-entry bound requests 64 KiB of stack)
+        int dev = 0, lds_max = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+        if (lds > (uint32_t)lds_max) return hipErrorInvalidValue;
+    }
     const bool march = (Q.S.n_msph + Q.S.n_mbox + Q.S.n_mtor + Q.S.n_msdf) != 0u;
     const bool user = Q.S.n_msdf != 0u;
     OmParamsDev P{};

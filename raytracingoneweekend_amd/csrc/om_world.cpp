@@ -488,6 +488,15 @@ om_status om_world_object_material(const om_world* w, uint32_t obj, om_material*
     return fail(OM_ERR_INVALID, "om_world_object_material: obj past the last object");
 }
 
+// the trees a freeze builds and AUTO's regime for them: host only
+om_status om_world_tree_info(const om_world* w, om_tree_info* out) {
+    if (!w || !out) return fail(OM_ERR_INVALID, "om_world_tree_info: null pointer");
+    FrozenWorld fw;
+    w->freeze(fw);
+    fill_tree_info(fw, plan_trees(fw), out);
+    return OM_OK;
+}
+
 om_status om_world_export(const om_world* w, int32_t kind, uint32_t i, float* out, uint32_t n) {
     if (!w || !out) return fail(OM_ERR_INVALID, "om_world_export: null pointer");
     if (kind == K_SPHERE || kind == K_CUBE) {

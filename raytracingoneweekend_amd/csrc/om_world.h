@@ -7,6 +7,7 @@
 #include "../../include/ottomarcher.h"
 #include "om_hostmath.h"
 #include "om_layout.h"
+#include "om_tuning.h"
 
 namespace om {
 
@@ -52,6 +53,9 @@ struct FrozenWorld {
     std::vector<uint32_t> b2leaves;    // its leaf table: (first_record << 8) | count
     uint32_t b2_depth = 0;             // its depth (stack bound)
     uint32_t b2_direct = 0;            // 1: leaf child codes carry OM_LEAF | first_record << 4 | count (no table read)
+    std::vector<OmBvh2NodeW> b2w;      // the BVH2 with 32-bit child codes (every world with a BVH2 whose records fit them)
+    uint32_t b2w_depth = 0;            // its depth (stack bound)
+    uint32_t b2_max_leaf = 0;          // records in the largest leaf of the BVH2
     std::vector<OmBvh4Node> b4nodes;   // 4-wide tree collapsed from b2nodes (leaf codes index b2leaves)
     std::vector<OmBvh4NodeH> b4h;      // the same tree breadth-first, half-precision boxes rounded outward
     uint32_t b4_depth = 0;             // its depth
@@ -71,7 +75,25 @@ struct TreePlan {
     uint32_t b4_stack = 0;         // 3 pushes per level + 3 spare entries for the unconditional pushes
     uint32_t b4_lds_bytes = 0;     // nodes (112 B each) + leaf table, rounded to 16, when within kB4LdsBudget
     uint32_t lds_bytes = 0;        // SBVH nodes + records when within kLdsBudget (at least 16)
+    // wide BVH2 (32-bit codes): usable when the records fit the direct leaf code
+    // (first < 2^27, count <= 15) and the depth the u32 lane stack's bound
+    bool b2w_ok = false;
+    uint32_t n_b2wnodes = 0, b2w_stack = 0;
 };
+
+// The wavefront's dynamic LDS per 512-lane workgroup in each BVH2 regime (om_wavefront.hip's
+// trace_lds, restated for the host-only om_world_tree_info): [lane stack][nodes or prefix].
+inline uint32_t wf_lds_b2_staged(uint32_t stack, uint32_t nodes, uint32_t leaves) {
+    return OM_WF_BLOCK * stack * 2u + ((nodes * (uint32_t)OM_B2_NODE_STRIDE + leaves * 4u + 15u) & ~15u);
+}
+inline uint32_t wf_lds_b2_l2(uint32_t stack, uint32_t nodes) {
+    const uint32_t cap = OM_WF_HYB_BYTES / (uint32_t)sizeof(OmBvh2NodeH);
+    return OM_WF_BLOCK * stack * 2u + (nodes < cap ? nodes : cap) * (uint32_t)sizeof(OmBvh2NodeH);
+}
+inline uint32_t wf_lds_b2_wide(uint32_t stack, uint32_t nodes) {
+    const uint32_t cap = OM_WF_HYBW_BYTES / (uint32_t)sizeof(OmBvh2NodeW);
+    return OM_WF_BLOCK * stack * 4u + (nodes < cap ? nodes : cap) * (uint32_t)sizeof(OmBvh2NodeW);
+}
 
 inline TreePlan plan_trees(const FrozenWorld& fw) {
     TreePlan p;
@@ -93,7 +115,34 @@ inline TreePlan plan_trees(const FrozenWorld& fw) {
     p.b4_stack = p.b4_ok ? b4_stack : 0u;
     const size_t b4_bytes = fw.b4nodes.size() * sizeof(OmBvh4Node) + fw.b2leaves.size() * 4u;
     p.b4_lds_bytes = (p.b4_ok && b4_bytes <= kB4LdsBudget) ? (uint32_t)((b4_bytes + 15u) & ~(size_t)15u) : 0u;
+    p.b2w_ok = !fw.b2w.empty() && fw.b2w.size() < OM_LEAFW && fw.srecs.size() < (1u << 27) && fw.b2_max_leaf <= 15u &&
+               fw.b2w_depth <= kB2WideStack &&
+               fw.offsets[K_N] <= OM_REC_GI;   // its kernels are the OM_REC_BARY forms: gi beside two kind bits
+    p.n_b2wnodes = p.b2w_ok ? (uint32_t)fw.b2w.size() : 0u;
+    p.b2w_stack = p.b2w_ok ? fw.b2w_depth : 0u;
     return p;
+}
+
+// om_tree_info of a frozen world: its trees, and the regime and wavefront LDS of OM_KERNEL_AUTO
+// (om_wavefront.hip's pick_trace; om_get_tree_info replaces the last two by the ctx's own choice).
+inline void fill_tree_info(const FrozenWorld& fw, const TreePlan& p, om_tree_info* out) {
+    out->records = (uint32_t)fw.srecs.size();
+    out->always_tested = (uint32_t)fw.always2.size();
+    out->b2_nodes = (uint32_t)fw.b2nodes.size();
+    out->b2_leaves = (uint32_t)fw.b2leaves.size();
+    // (past the 15-bit codes b2_depth is computed from colliding codes: the wide emission's is the tree's)
+    out->b2_depth = fw.b2w.empty() ? fw.b2_depth : fw.b2w_depth;
+    out->b2_max_leaf = fw.b2_max_leaf;
+    if (p.b2_ok) {
+        out->regime = p.b2_lds_bytes ? OM_TREE_LDS : OM_TREE_L2;
+        out->lds_bytes = p.b2_lds_bytes ? wf_lds_b2_staged(p.b2_stack, p.n_b2nodes, p.n_b2leaves) : wf_lds_b2_l2(p.b2_stack, p.n_b2nodes);
+    } else if (p.b2w_ok) {
+        out->regime = OM_TREE_WIDE;
+        out->lds_bytes = wf_lds_b2_wide(p.b2w_stack, p.n_b2wnodes);
+    } else {
+        out->regime = fw.bvh.size() <= 1u ? OM_TREE_NONE : OM_TREE_FALLBACK_BVH;
+        out->lds_bytes = 0u;
+    }
 }
 
 uint64_t bloom_hash(uint64_t id);      // utils.rs:94-107

@@ -21,6 +21,15 @@ fewer `--reps`.
     python tools/mesh_bench.py --root PARENT_TREE --reps 3 --groups 5 >> parent.jsonl
     python tools/mesh_bench.py --parent-json parent.jsonl        -> profiles/mesh/mesh_bench.json
 
+`--heightfield N` replaces the icosphere by an N x N-cell heightfield (512: 524 288 triangles, a tree past
+the BVH2's 15-bit child codes) and writes profiles/mesh/large_mesh_bench.json; the parent
+runs OM_KERNEL_BVH's traversal there.  `--kernel K` and `OM_LIB=variant.so --lib-tag T` print one line each
+for `--context-json` (this build's other kernels and build variants, same session):
+
+    python tools/mesh_bench.py --heightfield 512 --root PARENT_TREE --reps 3 --groups 5 >> parent.jsonl
+    python tools/mesh_bench.py --heightfield 512 --kernel bvh --reps 3 --groups 5 >> context.jsonl
+    python tools/mesh_bench.py --heightfield 512 --reps 20 --parent-json parent.jsonl --context-json context.jsonl
+
 The crossover that OM_BARY_TREE_MIN stands in for is not measured by this tool.
 """
 import argparse
@@ -68,9 +77,24 @@ def icosphere(level, center, radius):
     return np.ascontiguousarray(v, dtype=np.float32), np.asarray(faces, dtype=np.uint32)
 
 
-def mesh_world(om):
+def heightfield(n):
+    """scenes.heightfield(n, n, y = 0.3 sin(2.1 x) cos(1.7 z) + 1) over [-3, 3]^2, restated like the
+    icosphere: 2 n^2 triangles, float32"""
+    x = (-3.0 + 6.0 * np.arange(n + 1, dtype=np.float64) / n).astype(np.float32)
+    gx, gz = np.meshgrid(x, x, indexing="ij")
+    f32 = np.float32
+    gy = (f32(0.3) * np.sin(f32(2.1) * gx, dtype=f32) * np.cos(f32(1.7) * gz, dtype=f32) + f32(1.0)).astype(f32)
+    v = np.stack([gx, gy, gz], axis=-1).reshape(-1, 3)
+    i, j = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    a = (i * (n + 1) + j).ravel()
+    b, c, d = a + 1, a + (n + 1), a + (n + 2)
+    f = np.stack([np.stack([a, b, c], axis=1), np.stack([c, b, d], axis=1)], axis=1).reshape(-1, 3)
+    return np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(f, dtype=np.uint32)
+
+
+def mesh_world(om, hf=0):
     w = om.random_scene(0x5EED)
-    v, f = icosphere(LEVEL, (0., 1., 0.), 1.0)
+    v, f = heightfield(hf) if hf else icosphere(LEVEL, (0., 1., 0.), 1.0)
     mat = om.Material.new_metal_fuzz((0.8, 0.7, 0.5), 0.05)
     t0 = time.perf_counter()
     if hasattr(w, "add_triangles"):
@@ -91,8 +115,17 @@ def main():
     ap.add_argument("--root", default=ROOT, help="tree whose raytracingoneweekend_amd is measured")
     ap.add_argument("--parent-json", help="the lines of the parent commit's build (--root PARENT), same session")
     ap.add_argument("--no-render", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh", "mesh_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--heightfield", type=int, default=0, metavar="N",
+                    help="instead of the icosphere: an N x N-cell heightfield of 2 N^2 triangles (512: 524 288, a tree "
+                         "past the 15-bit child codes, DESIGN.md §5.18) -> profiles/mesh/large_mesh_bench.json")
+    ap.add_argument("--kernel", default="auto", help="kernel choice of the build under test; other than auto: one JSON "
+                                                     "line for --context-json, no file")
+    ap.add_argument("--context-json", help="lines of this build under other kernels (--kernel bvh / sbvh), same session")
+    ap.add_argument("--lib-tag", default=None, help="a label for an OM_LIB build variant (one JSON line, no file)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mesh", "large_mesh_bench.json" if args.heightfield else "mesh_bench.json")
     if not torch.cuda.is_available():
         sys.exit("mesh_bench: no HIP device; rates are only measured on the GPU")
     sys.path.insert(0, os.path.abspath(args.root))
@@ -103,13 +136,16 @@ def main():
     torch.cuda.set_stream(stream)
     sp = stream.cuda_stream
     cam = om.default_camera(W / H)
-    world, n_tri, how, t_add = mesh_world(om)
+    world, n_tri, how, t_add = mesh_world(om, args.heightfield)
     t0 = time.perf_counter()
-    fz = world.freeze(cam)
+    fz = world.freeze(cam, kernel=args.kernel)
     t_freeze = time.perf_counter() - t0
     L.check(L.lib.om_set_counting(fz.ctx, 0), fz.ctx)
-    out = {"build_id": L.build_id(), "device": torch.cuda.get_device_name(0),
-           "world": f"C1 (S-traced random_scene(0x5EED)) + icosphere level {LEVEL} at (0, 1, 0), radius 1",
+    what = (f"{args.heightfield} x {args.heightfield}-cell heightfield over [-3, 3]^2, y = 0.3 sin(2.1 x) cos(1.7 z) + 1"
+            if args.heightfield else f"icosphere level {LEVEL} at (0, 1, 0), radius 1")
+    out = {"build_id": L.build_id(), "device": torch.cuda.get_device_name(0), "kernel": args.kernel,
+           "tree_info": fz.tree_info() if hasattr(fz, "tree_info") else None, "lib_tag": args.lib_tag,
+           "world": f"C1 (S-traced random_scene(0x5EED)) + {what}",
            "triangles": n_tri, "mesh_added_by": how, "add_s": round(t_add, 4), "freeze_upload_s": round(t_freeze, 4),
            "frame": f"{W}x{H}", "warmup": args.warmup, "reps": args.reps, "groups": args.groups, "counting": False, "sets": {}}
     g = torch.Generator(device="cuda").manual_seed(7)
@@ -162,14 +198,25 @@ def main():
                 med = statistics.median(ms)
                 row[k]["parent"] = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
                                     "grays_per_s": round(row["rays"] / med / 1e6, 5)}
-                row[k]["speedup_over_parent"] = round(med / row[k]["ms_median"], 1)
+                row[k]["speedup_over_parent"] = round(med / row[k]["ms_median"], 2 if args.heightfield else 1)
+                # no slower than the parent, the margin being the parent's own min-max spread
+                row[k]["within_or_better_than_parent_spread"] = bool(row[k]["ms_median"] <= max(ms))
         if "render" in out and all("render" in run for run in runs):
             ms = [x for run in runs for x in run["render"]["ms"]]
             out["render"]["parent"] = {"ms": [round(x, 3) for x in ms],
                                        "msamples_per_s": round(W * H * SPP / statistics.median(ms) / 1e3, 1)}
-            out["render"]["speedup_over_parent"] = round(statistics.median(ms) / statistics.median(out["render"]["ms"]), 1)
+            out["render"]["speedup_over_parent"] = round(statistics.median(ms) / statistics.median(out["render"]["ms"]),
+                                                         2 if args.heightfield else 1)
+            out["render"]["faster_than_parent_beyond_its_spread"] = bool(max(out["render"]["ms"]) < min(ms))
+    if args.context_json:
+        with open(args.context_json) as f:
+            ctx = [json.loads(ln) for ln in f.read().splitlines() if ln.startswith("{")]
+        out["context"] = [{"kernel": r["kernel"], "lib_tag": r.get("lib_tag"), "tree_info": r.get("tree_info"),
+                           "render_ms": r.get("render", {}).get("ms"),
+                           "sets": {n: {k: {"ms_median": s[k]["ms_median"], "grays_per_s": s[k]["grays_per_s"]}
+                                        for k in ("closest_hit", "any_hit")} for n, s in r["sets"].items()}} for r in ctx]
     print(json.dumps(out))
-    if args.root == ROOT:
+    if args.root == ROOT and args.kernel == "auto" and not args.lib_tag:
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
