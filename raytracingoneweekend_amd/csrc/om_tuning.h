@@ -115,12 +115,26 @@
 #define OM_WF_ADAPTIVE_TAIL 8
 #endif
 // Queue segments (= bounce workgroups) per CU: OM_WF_LANES_PER_CU / OM_WF_BLOCK; marched worlds
-// and BVH2s read through L2 use the WIDE count.
+// and BVH2s read through L2 use the WIDE count.  2048 is one resident round of
+// workgroups: with bounce 0's even deal (OM_WF_DEAL_BLOCKS) the segments are alike, and the second
+// round per slot that evened out the stripes' unequal segments (4096, through r07) no longer pays.
 #ifndef OM_WF_LANES_PER_CU
-#define OM_WF_LANES_PER_CU 4096
+#define OM_WF_LANES_PER_CU 2048
 #endif
 #ifndef OM_WF_LANES_PER_CU_WIDE
 #define OM_WF_LANES_PER_CU_WIDE 8192
+#endif
+// Bounce 0's deal (om_deal.h): consecutive 64-sample blocks a workgroup takes
+// before the round-robin moves on to the next workgroup.  1 spreads every stripe of the frame over
+// all segments, but a later bounce's wave then holds the survivors of tiles from all over the frame;
+// larger values keep neighbouring tiles' paths together in the segment (and their candidate lists
+// in one CU's scalar cache).  C1, plain bench, alternating on one box, parent (contiguous ranges)
+// 7226, 7293: 1 / 2 / 4 / 8 -> 7030, 6980 / 7097, 7092 / 7256, 7192 / 7335, 7345; a second box,
+// parent 7375, 7344: 8 / 16 / 32 / 64 -> 7508, 7479 / 7370, 7401 / 7565, 7541 / 7502, 7516, and
+// with OM_WF_LANES_PER_CU 2048: 1 / 8 / 32 -> 7440, 7415 / 7766, 7752 / 7470, 7447
+// (profiles/even_deal; one stream: parent 5252, 1 -> 5811, 8 -> 5988 Msamples/s).
+#ifndef OM_WF_DEAL_BLOCKS
+#define OM_WF_DEAL_BLOCKS 8
 #endif
 // k_accumulate: samples whose loads are issued together before their adds in sample order
 #ifndef OM_ACC_GROUP

@@ -29,6 +29,7 @@
 #include "om_device.h"
 #include "om_trace.h"
 #include "om_tuning.h"
+#include "om_deal.h"
 
 using namespace omd;
 
@@ -138,12 +139,10 @@ using MarchedC2Lds = MarchedExactLds<2, 1, 1>;
 enum { MV_ARRAYS = 0, MV_EXACT_C2_LDS = 1 };
 template <int TR>
 __host__ __device__ constexpr bool exact_view_built() { return TR == TR_BRUTE || TR == TR_BVH2_LDS; }   // (not the TR_BARY forms)
-// Segment capacity rounded up to whole waves, so that a bounce-0 wave is exactly one 8x8 tile of
-// one sample (tile-ordered pixel lists hold whole tiles).
-__host__ __device__ inline uint32_t seg_capacity(uint64_t paths, uint32_t nseg) {
-    const uint64_t c = (paths + nseg - 1) / nseg;
-    return (uint32_t)((c + 63u) / 64u * 64u);
-}
+// Bounce 0's deal of a batch of `paths` camera samples over nseg workgroups (om_deal.h): whole
+// 64-sample blocks, so that a bounce-0 wave is exactly one 8x8 tile of one sample (tile-ordered
+// pixel lists hold whole tiles).  Its capacity() is the segment capacity of the batch's queues.
+__host__ __device__ inline Deal batch_deal(uint64_t paths, uint32_t nseg) { return make_deal(paths, nseg, OM_WF_DEAL_BLOCKS); }
 
 extern __shared__ __attribute__((aligned(16))) uint4 wf_lds[];
 
@@ -441,8 +440,8 @@ __device__ __forceinline__ bool gen_path(const OmParamsDev& P, const Gen& R, uin
 }
 
 // ---------------------------------------------------------------- bounce
-// Workgroup s: the paths of segment s of queue `in` (FIRST: the camera samples
-// [s*segcap, (s+1)*segcap) of the batch) -> survivors into segment s of `out`.
+// Workgroup s: the paths of segment s of queue `in` (FIRST: the 64-sample blocks of the batch
+// that batch_deal gives workgroup s) -> survivors into segment s of `out`.
 // HIT (split march pipeline): no trace here; the (closest, winner) of every path of the
 // segment was written to `hitbuf` (queue-slot order) by k_march.
 // Work distribution: every wave takes 64-path chunks of the segment from an
@@ -457,7 +456,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
                                                  const float2* __restrict__ hitbuf, uint32_t* __restrict__ tail_next) {
     const uint64_t seg0 = (uint64_t)blockIdx.x * G.segcap;
     uint32_t n, stride = R.n_pixels;
-    uint64_t first0 = seg0;                 // FIRST: the batch's first sample of this workgroup
+    Deal dl{};                              // FIRST: the batch's deal; n counts this workgroup's blocks
     if (FIRST) {
         // the batch's traced tail claims paths from this word: zeroed here, launches ahead of it
         // on the same stream (no memset, no launch of its own)
@@ -467,11 +466,9 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
             const AdPlan pl = uniform_load(R.ad.plan);
             stride = pl.c;
             paths = (uint64_t)pl.c * ad_batch(pl.c, pl.done, R.ad.j, R.ad.A);
-            first0 = (uint64_t)blockIdx.x * seg_capacity(paths, G.nseg);
-            n = first0 < paths ? (uint32_t)std::min<uint64_t>(seg_capacity(paths, G.nseg), paths - first0) : 0u;
-        } else {
-            n = seg0 < paths ? (uint32_t)std::min<uint64_t>(G.segcap, paths - seg0) : 0u;
         }
+        dl = batch_deal(paths, G.nseg);
+        n = dl.blocks_of(blockIdx.x);
     } else {
         n = count_in[blockIdx.x];
     }
@@ -487,16 +484,18 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
     WorkT<COUNT, false, tr_bary(TR)> w;
     uint32_t segs = 0;
     const uint32_t lane = __lane_id();
-    for (uint32_t chunk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); chunk * 64u < n;) {   // wave-uniform
-        const uint32_t jj = chunk * 64u + lane;
+    const uint32_t chunks = FIRST ? n : (n + 63u) / 64u;
+    for (uint32_t chunk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); chunk < chunks;) {   // wave-uniform
+        // FIRST: camera sample i of the batch (the deal's chunk-th block of this workgroup, the
+        // batch's last block partial); else slot i of the in queue
+        const uint64_t i = FIRST ? dl.block(blockIdx.x, chunk) * 64u + lane : seg0 + chunk * 64u + lane;
         bool keep = false;
         Path p;
         uint32_t p_pixel = 0;
-        if (jj < n) {
-            const uint64_t i = seg0 + jj;
+        if (FIRST ? i < dl.paths : chunk * 64u + lane < n) {
             bool live = true;
             if (FIRST) {
-                live = gen_path(P, R, stride, first0 + jj, p, p_pixel, res_id);
+                live = gen_path(P, R, stride, i, p, p_pixel, res_id);
             } else {
                 load_ray(in, i, p);
                 load_rest(in, i, p);       // issued before the trace: its latency hides behind it
@@ -551,32 +550,30 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
 }
 
 // ---------------------------------------------------------------- split march pipeline
-// k_raygen: the camera samples [s*segcap, (s+1)*segcap) of the batch; the taken ones are
-// compacted into segment s of `out` (bounce 0 of the split pipeline reads them from there).
+// k_raygen: the 64-sample blocks of the batch that batch_deal gives workgroup s; the taken samples
+// are compacted into segment s of `out` (bounce 0 of the split pipeline reads them from there).
 template <bool COUNT>
 __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_raygen(OmParamsDev P, Seg G, Gen R, Queue out,
                                                  uint32_t* __restrict__ count_out, uint32_t* __restrict__ res_id) {
     const uint64_t seg0 = (uint64_t)blockIdx.x * G.segcap;
-    uint64_t paths = (uint64_t)R.n_pixels * R.batch, first0 = seg0;
-    uint32_t n, stride = R.n_pixels;
+    uint64_t paths = (uint64_t)R.n_pixels * R.batch;
+    uint32_t stride = R.n_pixels;
     if (R.ad.list) {                        // adaptive: the stream's live list x the planned samples
         const AdPlan pl = uniform_load(R.ad.plan);
         stride = pl.c;
         paths = (uint64_t)pl.c * ad_batch(pl.c, pl.done, R.ad.j, R.ad.A);
-        first0 = (uint64_t)blockIdx.x * seg_capacity(paths, G.nseg);
-        n = first0 < paths ? (uint32_t)std::min<uint64_t>(seg_capacity(paths, G.nseg), paths - first0) : 0u;
-    } else {
-        n = seg0 < paths ? (uint32_t)std::min<uint64_t>(G.segcap, paths - seg0) : 0u;
     }
+    const Deal dl = batch_deal(paths, G.nseg);
+    const uint32_t nblk = dl.blocks_of(blockIdx.x);
     __shared__ uint32_t q_out;
     if (threadIdx.x == 0) q_out = 0u;
     __syncthreads();
     const uint32_t lane = __lane_id();
-    for (uint32_t base = 0; base < n; base += kBlk) {
-        const uint32_t jj = base + threadIdx.x;
+    for (uint32_t c = threadIdx.x >> 6; c < nblk; c += kBlk / 64u) {   // wave c of the workgroup: its blocks c, c + 8, ...
+        const uint64_t i = dl.block(blockIdx.x, c) * 64u + lane;   // (the batch's last block is partial)
         Path p;
         uint32_t pixel;
-        const bool keep = jj < n && gen_path(P, R, stride, first0 + jj, p, pixel, res_id);
+        const bool keep = i < dl.paths && gen_path(P, R, stride, i, p, pixel, res_id);
         const uint64_t m = __ballot(keep);
         uint32_t obase = 0u;
         if (lane == 0 && m) obase = atomicAdd(&q_out, (uint32_t)__popcll(m));
@@ -1508,9 +1505,10 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
                            : adaptive ? OM_WF_ADAPTIVE_TAIL
                            : max_paths > (1ull << 25) ? kTailBigBatch : kTailDefault;
     const uint32_t lanes_per_cu = (march || l2_tree) ? OM_WF_LANES_PER_CU_WIDE : OM_WF_LANES_PER_CU;
-    uint32_t nseg = (uint32_t)std::min<uint64_t>((max_paths + kBlk - 1) / kBlk, (uint64_t)cus * (lanes_per_cu / kBlk));
-    nseg = (nseg + kTailSpb - 1) / kTailSpb * kTailSpb;
-    const uint32_t segcap = seg_capacity(max_paths, nseg);
+    const uint32_t nseg = deal_segments(max_paths, (uint32_t)cus, lanes_per_cu, kBlk, kTailSpb);
+    // the fullest workgroup's share of the largest batch's deal (adaptive: max_paths bounds every
+    // batch the device plans, and capacity() grows with the paths)
+    const uint32_t segcap = batch_deal(max_paths, nseg).capacity();
     // (+ 1: the traced tail's claim counter, run_batch)
     hipError_t e = grow(B, (uint64_t)nseg * segcap, (depth_cap + 1u) * nseg + 1u, (int)ns);
     if (e != hipSuccess) { err = "wavefront buffer allocation failed"; return e; }
@@ -1591,7 +1589,7 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
         } else {
             const uint32_t done = done_at[i];
             b = done_at[i + 1] - done;
-            G.segcap = seg_capacity((uint64_t)n_px * b, nseg);
+            G.segcap = batch_deal((uint64_t)n_px * b, nseg).capacity();
             R.done = done;
             grid_a = (n_px + kBlk - 1) / kBlk;
         }

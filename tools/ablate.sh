@@ -29,10 +29,18 @@ declare -A V=(
   [twg3]="$COMMON $DEV -DOM_WF_TAIL_WGS_PER_CU=3"
   [twg4]="$COMMON $DEV -DOM_WF_TAIL_WGS_PER_CU=4"
   # segments per CU (lanes per CU / workgroup size), traced and wide (marched, L2 BVH2)
-  [lpc2k]="$COMMON $DEV -DOM_WF_LANES_PER_CU=2048"
+  [lpc4k]="$COMMON $DEV -DOM_WF_LANES_PER_CU=4096"
   [lpc8k]="$COMMON $DEV -DOM_WF_LANES_PER_CU=8192"
   [mlpc4k]="$COMMON $DEV -DOM_WF_LANES_PER_CU_WIDE=4096"
   [mlpc16k]="$COMMON $DEV -DOM_WF_LANES_PER_CU_WIDE=16384"
+  # bounce 0's deal: consecutive 64-sample blocks per workgroup (default 8)
+  [deal1]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=1"
+  [deal2]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=2"
+  [deal4]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=4"
+  [deal6]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=6"
+  [deal12]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=12"
+  [deal16]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=16"
+  [deal32]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=32"
   # S-10k: bytes of breadth-first BVH2 prefix staged in LDS (0 = all nodes through L2)
   [hyb0]="$COMMON $DEV -DOM_WF_HYB_BYTES=0"
   [hyb16k]="$COMMON $DEV -DOM_WF_HYB_BYTES=16384"
