@@ -390,9 +390,11 @@ om_status om_set_counting(om_ctx* ctx, int32_t enable);
 enum { OM_PIPELINE_MEGAKERNEL = 0, OM_PIPELINE_WAVEFRONT = 1, OM_PIPELINE_AUTO = 2 };
 om_status om_set_pipeline(om_ctx* ctx, int32_t pipeline);
 /* Wavefront pipeline: bounces >= `bounce` are finished by one persistent tail launch
- * (lanes run whole remaining paths); 0 = default (16; 1 for worlds with marched
- * primitives, 10 when the BVH2 is too big for LDS, 8 for adaptive calls, 24 for batches
- * above 2^25 paths),
+ * (lanes run whole remaining paths); 0 = default (17; 1 for worlds with marched
+ * primitives, 11 when the BVH2 is too big for LDS, 9 for adaptive calls, 25 for batches
+ * above 2^25 paths: traced worlds run bounces 0 and 1 in one launch, and their defaults
+ * keep 16 / 10 / 8 / 24 launches ahead of the tail; the tail never starts before the first
+ * queue that launch writes, bounce 2's),
  * >= max_depth = no tail.  A pure
  * scheduling knob: results are bit-identical for every value. */
 om_status om_set_tail_bounce(om_ctx* ctx, uint32_t bounce);

@@ -136,6 +136,17 @@
 #ifndef OM_WF_DEAL_BLOCKS
 #define OM_WF_DEAL_BLOCKS 8
 #endif
+// Traced worlds: 1, the launch of bounce 0 also traces and shades bounce 1 on the lanes whose path
+// goes on, and compacts them into bounce 2's queue (k_bounce's FUSE): the
+// 64 B per path that bounce 0 would write and bounce 1 read back (C1: 26.0 M paths, 3.3 GB per 16-spp
+// batch) stay in registers.  Bounce 0's waves are 8x8 tiles and the paths that end there end in sky,
+// so 20.6 % of C1's blocks have no survivor and skip the second segment, and the others trace it
+// at 98.6 % lane occupancy (tests/cpp/fused_census.cpp, profiles/fused_b01/census.jsonl).  The
+// default tail thresholds count per-bounce launches, so the tail starts one bounce later and the
+// launches per batch are the same.  0: bounce 1 is a launch of its own over queue 1.
+#ifndef OM_WF_FUSE_B1
+#define OM_WF_FUSE_B1 1
+#endif
 // k_accumulate: samples whose loads are issued together before their adds in sample order
 #ifndef OM_ACC_GROUP
 #define OM_ACC_GROUP 8

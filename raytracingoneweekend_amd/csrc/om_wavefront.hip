@@ -98,7 +98,12 @@ constexpr uint32_t kTailSpb = OM_WF_TAIL_SPB;                     // marched tai
 constexpr uint32_t kTailWgsPerCu = OM_WF_TAIL_WGS_PER_CU;         // traced tail: resident workgroups per CU
 constexpr uint32_t kWaves = kBlk / 64;                            // waves of a workgroup
 static_assert(kBlk % 64 == 0 && kTailWgsPerCu >= 1u, "whole waves; a tail grid");
-// first bounce handled by the tail kernel.  On the balanced tail an earlier start measures faster
+// traced worlds: the launch of bounce 0 runs bounce 1 as well (om_tuning.h, k_bounce's FUSE); the
+// first queue it writes is then bounce 2's
+constexpr bool kFuseB1 = OM_WF_FUSE_B1 != 0;
+// Per-bounce launches (bounce 0's included) before the tail kernel takes over: without the fused
+// launch also the first bounce of the tail, with it one bounce later (tail_first), so that the
+// launch counts per batch are the same either way.  On the balanced tail an earlier start measures faster
 // (C1, 1 workgroup per CU: T = 8 / 10 / 12 / 16 -> 7307 / 7297 / 7281 / 7227 Msamples/s, means of
 // three runs, parent 7125); the threshold stays where tests/test_gpu_production_shapes.py pins the
 // launch counts of the bench's shapes
@@ -448,12 +453,17 @@ __device__ __forceinline__ bool gen_path(const OmParamsDev& P, const Gen& R, uin
 // LDS counter and appends its survivors with one LDS atomic, so the 8 waves never wait for each
 // other.  Queue order within a segment then depends on which wave finishes first; results are
 // keyed by slot and the RNG by (pixel, sample), never by queue position.
+// FUSE (traced worlds' FIRST launch under OM_WF_FUSE_B1): the lanes whose path
+// goes on after bounce 0 trace and shade bounce 1 in place, on the staged tree, and only then are
+// compacted: `out` is bounce 2's queue, and the 64 B a bounce-1 path would be written and read
+// back with never reach HBM.  A wave with no survivor (a tile of sky) skips the second segment.
 template <int TR, bool COUNT, bool MARCH, bool FIRST, bool HIT = false, bool USER = MARCH>
 __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmParamsDev P, Seg G, Gen R, Queue in,
                                                  const uint32_t* __restrict__ count_in, Queue out,
                                                  uint32_t* __restrict__ count_out, float4* __restrict__ res,
                                                  uint32_t* __restrict__ res_id, unsigned long long* __restrict__ counters,
                                                  const float2* __restrict__ hitbuf, uint32_t* __restrict__ tail_next) {
+    constexpr bool FUSE = FIRST && !MARCH && !HIT && kFuseB1;
     const uint64_t seg0 = (uint64_t)blockIdx.x * G.segcap;
     uint32_t n, stride = R.n_pixels;
     Deal dl{};                              // FIRST: the batch's deal; n counts this workgroup's blocks
@@ -488,46 +498,64 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
     for (uint32_t chunk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); chunk < chunks;) {   // wave-uniform
         // FIRST: camera sample i of the batch (the deal's chunk-th block of this workgroup, the
         // batch's last block partial); else slot i of the in queue
-        const uint64_t i = FIRST ? dl.block(blockIdx.x, chunk) * 64u + lane : seg0 + chunk * 64u + lane;
-        bool keep = false;
+        // (FUSE: a batch has at most 2^OM_WF_MAX_PATHS_LOG2 samples, so the sum fits 32 bits, and no
+        // 64-bit lane index is kept in registers over the chunk loop)
+        const uint64_t i = FUSE  ? (uint64_t)((uint32_t)(dl.block(blockIdx.x, chunk) * 64u) + lane)
+                         : FIRST ? dl.block(blockIdx.x, chunk) * 64u + lane : seg0 + chunk * 64u + lane;
+        bool keep = false;                 // the lane holds a live path
         Path p;
         uint32_t p_pixel = 0;
         if (FIRST ? i < dl.paths : chunk * 64u + lane < n) {
-            bool live = true;
             if (FIRST) {
-                live = gen_path(P, R, stride, i, p, p_pixel, res_id);
+                // FUSE: the divisor of gen_path's i / stride made opaque per chunk, so that the
+                // reciprocal of that division is worked out here (a dozen instructions per 64
+                // paths) and not kept in a vector register over the chunk loop, where it spilled
+                uint32_t st = stride;
+                if (FUSE) asm volatile("" : "+s"(st));
+                keep = gen_path(P, R, st, i, p, p_pixel, res_id);
             } else {
                 load_ray(in, i, p);
                 load_rest(in, i, p);       // issued before the trace: its latency hides behind it
+                keep = true;
             }
-            if (live) {
-                float closest;
-                int best;
+        }
+        // FIRST with candidate lists: bounce 0's closest hit from the tile's list (ahead of the segment
+        // loop, whose trace is the tree's)
+        float closest = 0.0f;
+        int best = -1;
+        const bool listed = FIRST && !HIT && (tr_base(TR) == TR_BVH2_LDS || tr_base(TR) == TR_BVH2_GLOBAL || tr_base(TR) == TR_BVH2_WIDE) && R.tile_off;
+        if (listed && keep) {
+            const uint32_t line = p_pixel / P.width;
+            const uint32_t tile = (p_pixel - line * P.width) / 8u + (line / 8u) * P.tiles_x;
+            closest = P.tmax;
+            // a wave within one tile (all but where partial tiles meet) reads its list
+            // and records with scalar loads
+            const uint32_t t0 = __builtin_amdgcn_readfirstlane(tile);
+            if (__ballot(tile != t0) == 0)
+                best = traced_tiles<true>(S, R.tile_off, R.tile_idx, t0, p.o, p.d, P.tmin, closest, w, R.tile_tnear);
+            else
+                best = traced_tiles(S, R.tile_off, R.tile_idx, tile, p.o, p.d, P.tmin, closest, w);
+            if (MARCH) {
+                float tm;
+                const int mg = march(S, p.o, p.d, P.tmin, P.tmax, closest, P.march_steps, tm, w);
+                if (mg >= 0) { best = mg; closest = tm; }
+            }
+        }
+        // one segment; FUSE: a second one for the wave's paths that go on, before any of them is queued
+        // (one loop, so that the tree's trace and shade_path are in the kernel once)
+#pragma clang loop unroll(disable)
+        for (uint32_t sg = 0u;; ++sg) {
+            if (keep) {
                 if (HIT) {
                     const float2 h = hitbuf[i];
                     closest = h.x; best = __float_as_int(h.y);
-                } else if (FIRST && (tr_base(TR) == TR_BVH2_LDS || tr_base(TR) == TR_BVH2_GLOBAL || tr_base(TR) == TR_BVH2_WIDE) && R.tile_off) {
-                    const uint32_t line = p_pixel / P.width;
-                    const uint32_t tile = (p_pixel - line * P.width) / 8u + (line / 8u) * P.tiles_x;
-                    closest = P.tmax;
-                    // a wave within one tile (all but where partial tiles meet) reads its list
-                    // and records with scalar loads
-                    const uint32_t t0 = __builtin_amdgcn_readfirstlane(tile);
-                    if (__ballot(tile != t0) == 0)
-                        best = traced_tiles<true>(S, R.tile_off, R.tile_idx, t0, p.o, p.d, P.tmin, closest, w, R.tile_tnear);
-                    else
-                        best = traced_tiles(S, R.tile_off, R.tile_idx, tile, p.o, p.d, P.tmin, closest, w);
-                    if (MARCH) {
-                        float tm;
-                        const int mg = march(S, p.o, p.d, P.tmin, P.tmax, closest, P.march_steps, tm, w);
-                        if (mg >= 0) { best = mg; closest = tm; }
-                    }
-                } else {
+                } else if (!(listed && sg == 0u)) {
                     best = trace<TR, MARCH>(S, P, T, p.o, p.d, closest, w);
                 }
                 keep = shade_path<MARCH, USER>(S, P, depth_cap, p, closest, best, res, res_id);
                 if (COUNT) segs++;
             }
+            if (!FUSE || sg == 1u || __ballot(keep) == 0) break;   // wave-uniform
         }
         const uint64_t m = __ballot(keep);
         uint32_t obase = 0u, nc = 0u;
@@ -537,7 +565,11 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
         }
         obase = __builtin_amdgcn_readfirstlane(obase);
         chunk = __builtin_amdgcn_readfirstlane(nc);
-        if (keep) store_path(out, seg0 + obase + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)), p);
+        // the lane's rank among the wave's survivors (FUSE: counted by the mbcnt pair, no lane mask
+        // kept in registers over the chunk loop)
+        const uint32_t rank = FUSE ? __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))
+                                   : (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (keep) store_path(out, seg0 + obase + rank, p);
     }
     __syncthreads();
     if (threadIdx.x == 0) count_out[blockIdx.x] = q_out;
@@ -1249,6 +1281,10 @@ Queue queue(QueueSet& B, int k) { return Queue{B.q[k][0], B.q[k][1], B.q[k][2], 
 inline uint32_t tail_pre_off(uint32_t lds) { return (lds + 15u) & ~15u; }
 inline uint32_t tail_lds(uint32_t lds, uint32_t nseg) { return tail_pre_off(lds) + (nseg + 1u) * 4u; }
 
+// Rows of nseg segment counts a queue set holds: one per bounce and the counts behind the last one;
+// the fused first launch writes row 2 whatever the depth.
+inline uint32_t count_rows(uint32_t depth_cap) { return std::max<uint32_t>(depth_cap, kFuseB1 ? 2u : 1u) + 1u; }
+
 // One batch: bounce 0 .. tail_at-1 as per-bounce launches, then the tail launch, all on `st`;
 // returns the number of bounce-family launches.
 template <int TR, bool COUNT, bool MARCH>
@@ -1259,7 +1295,7 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
     uint32_t launches = 0;
     const bool exact = MARCH && L.S.n_msdf == 0u && MarchedC2Lds::matches(L.S.n_msph, L.S.n_mbox, L.S.n_mtor);
     // the traced tail's claim counter: the word behind the set's per-bounce counts
-    uint32_t* const tail_next = B.counts + (size_t)(depth_cap + 1u) * G.nseg;
+    uint32_t* const tail_next = B.counts + (size_t)count_rows(depth_cap) * G.nseg;
     auto tail = [&](const Queue& in, const uint32_t* cin) {
         const int ti = each ? tm.begin(st) : -1;
         if constexpr (MARCH) {
@@ -1313,11 +1349,14 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
         }
         return launches;
     } else {
-    for (uint32_t bounce = 0; bounce < depth_cap; ++bounce) {
-        const Queue in = queue(B, bounce & 1u), out = queue(B, (bounce + 1u) & 1u);
+    // (fused first launch: bounces 0 and 1, its out queue is bounce 2's; the first queue the tail or a
+    // per-bounce launch can read is the one that launch wrote, whatever tail_at asks for)
+    for (uint32_t bounce = 0, next; bounce < depth_cap; bounce = next) {
+        next = bounce + (bounce == 0 && kFuseB1 ? 2u : 1u);
+        const Queue in = queue(B, bounce & 1u), out = queue(B, next & 1u);
         const uint32_t* cin = B.counts + (size_t)bounce * G.nseg;
         if (bounce > 0 && bounce >= tail_at) return tail(in, cin);
-        uint32_t* cout = B.counts + (size_t)(bounce + 1u) * G.nseg;
+        uint32_t* cout = B.counts + (size_t)next * G.nseg;
         const int ti = each ? tm.begin(st) : -1;
         if (bounce == 0)
             hipLaunchKernelGGL((k_bounce<TR, COUNT, MARCH, true>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, R, in,
@@ -1500,17 +1539,19 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
     const bool march = (L.S.n_msph + L.S.n_mbox + L.S.n_mtor + L.S.n_msdf) != 0u;
     // trees read through L2 (the wide BVH2 among them)
     const bool l2_tree = tr_base(tr) == TR_BVH2_GLOBAL || tr_base(tr) == TR_BVH4_GLOBAL || tr_base(tr) == TR_BVH2_WIDE;
+    // the first bounce of the tail: the caller's (om_set_tail_bounce), or the default count of
+    // per-bounce launches, which the fused first launch carries one bounce further
     const uint32_t tail_at = L.tail_bounce ? L.tail_bounce
-                           : march ? kTailMarched : l2_tree ? kTailL2
-                           : adaptive ? OM_WF_ADAPTIVE_TAIL
-                           : max_paths > (1ull << 25) ? kTailBigBatch : kTailDefault;
+                           : march ? kTailMarched
+                           : (l2_tree ? kTailL2 : adaptive ? OM_WF_ADAPTIVE_TAIL
+                              : max_paths > (1ull << 25) ? kTailBigBatch : kTailDefault) + (kFuseB1 ? 1u : 0u);
     const uint32_t lanes_per_cu = (march || l2_tree) ? OM_WF_LANES_PER_CU_WIDE : OM_WF_LANES_PER_CU;
     const uint32_t nseg = deal_segments(max_paths, (uint32_t)cus, lanes_per_cu, kBlk, kTailSpb);
     // the fullest workgroup's share of the largest batch's deal (adaptive: max_paths bounds every
     // batch the device plans, and capacity() grows with the paths)
     const uint32_t segcap = batch_deal(max_paths, nseg).capacity();
     // (+ 1: the traced tail's claim counter, run_batch)
-    hipError_t e = grow(B, (uint64_t)nseg * segcap, (depth_cap + 1u) * nseg + 1u, (int)ns);
+    hipError_t e = grow(B, (uint64_t)nseg * segcap, count_rows(depth_cap) * nseg + 1u, (int)ns);
     if (e != hipSuccess) { err = "wavefront buffer allocation failed"; return e; }
     const uint32_t lds = trace_lds(tr, L.S);
     // the traced tail: a resident grid, and the segment-count prefix in LDS behind the tree

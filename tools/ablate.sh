@@ -41,6 +41,9 @@ declare -A V=(
   [deal12]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=12"
   [deal16]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=16"
   [deal32]="$COMMON $DEV -DOM_WF_DEAL_BLOCKS=32"
+  # traced worlds: bounce 1 inside the bounce-0 launch (default 1), or as a launch of its own
+  [fuse0]="$COMMON $DEV -DOM_WF_FUSE_B1=0"
+  [fuse1]="$COMMON $DEV -DOM_WF_FUSE_B1=1"
   # S-10k: bytes of breadth-first BVH2 prefix staged in LDS (0 = all nodes through L2)
   [hyb0]="$COMMON $DEV -DOM_WF_HYB_BYTES=0"
   [hyb16k]="$COMMON $DEV -DOM_WF_HYB_BYTES=16384"
