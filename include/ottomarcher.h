@@ -281,6 +281,23 @@ om_status om_render(om_ctx* ctx, const om_camera* cam, const om_render_params* p
  * One record per ray, the reference loop's answer for it, through the traversal, tie rule and
  * HitRecord code the render kernels use for the ctx's kernel choice and uploaded world (rays with
  * NaN or infinite components, which no camera produces, run the reference loop itself).
+ * Domain of that guarantee: OM_KERNEL_BRUTE gives the reference loop's record for
+ * every ray.  The culling kernels (every other choice, AUTO included) give it while the float32
+ * rounding of Sphere::hit stays inside the absolute box margin.  Two cases that it cannot are kept
+ * away from the culls: a sphere or ellipsoid whose margin does not cover the worst case of that
+ * rounding, 2^-21 D^2 rmax / rmin^2, for a ray origin D = 16 away (radius below about 0.1, or a
+ * strongly flattened ellipsoid) is tested outside the trees, and om_hit_rays* / om_occluded_rays*
+ * answer with the reference loop a ray whose origin is so far from the box of the bounded primitives
+ * that the slab test itself is no finer than the margin (2 sqrt(3) d + the box's diagonal above 8192);
+ * om_render does the same for a whole call whose camera is that far.
+ * Measured: the records are the reference's for ray origins inside the world or 13 away from it, for
+ * primitives of any size, also in a world 1.4e5 from the coordinate origin, and for origins from 1e4
+ * away on.  Between 16 and the slab test's reach the margin covers the typical rounding only: the
+ * records are not the reference's for spheres of radius 0.2 to 1 seen from 1e3 away (from 1e2 with
+ * OM_KERNEL_CULLED).  There a ray that the reference's sphere test accepts
+ * within its rounding error of the silhouette can get the record of what lies behind that sphere, or
+ * a miss; a hit is never invented.
+ * tests/test_gpu_scale.py pins these cases as expected failures.
  *   om_ray   the `Ray { orig, dir }` literal (ray.rs:5-8).  dir is used as given, never normalised
  *            on the device.  The precondition is a unit direction (Ray::new's invariant, ray.rs:12,
  *            which every ray the renderer traces meets): the march's step and the traversal's

@@ -45,7 +45,12 @@ struct Box {
 
 struct Item { Box b; double c[3]; uint32_t gi; };
 
-// Inflate a box well beyond f32 rounding of the exact tests.
+// Inflate a box beyond the f32 rounding of the exact tests at the scene scale.  The margin is
+// absolute; Sphere::hit accepts rays that pass an ellipsoid at up to about 6e-8 * (D^2 + C*D) / (2r)
+// outside it (ray origin D away, world coordinates up to C, smallest semi-axis r), which passes
+// this margin for r = 0.2 from D of about 100 on and for r <= 9e-3 at D = 13 (thin_sphere below keeps
+// out of the trees what the worst case of that error can reach from OM_SPHERE_REACH away): DESIGN.md §5.3 states the domain, tests/test_scale_conservative.py measures
+// it from these very boxes.
 Box inflate(Box b) {
     double mag = 0.0;
     for (int i = 0; i < 3; ++i) mag = std::max(mag, std::max(std::fabs(b.lo[i]), std::fabs(b.hi[i])));
@@ -199,19 +204,67 @@ uint16_t half_out(float x, bool up) {
 }
 
 
+// Smallest and largest semi-axis of an ellipsoid: the extreme singular values of the 3x3 linear
+// part (closed form for the eigenvalues of the symmetric A^T A, in double).
+void semi_axes(const Mat4& l2w, double& rmin, double& rmax) {
+    double s[3][3];
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) { s[i][j] = 0; for (int k = 0; k < 3; ++k) s[i][j] += (double)l2w.r[k].e[i] * (double)l2w.r[k].e[j]; }
+    const double p1 = s[0][1] * s[0][1] + s[0][2] * s[0][2] + s[1][2] * s[1][2];
+    const double q = (s[0][0] + s[1][1] + s[2][2]) / 3.0;
+    const double p2 = (s[0][0] - q) * (s[0][0] - q) + (s[1][1] - q) * (s[1][1] - q) + (s[2][2] - q) * (s[2][2] - q) + 2.0 * p1;
+    double lo = std::min(s[0][0], std::min(s[1][1], s[2][2])), hi = std::max(s[0][0], std::max(s[1][1], s[2][2]));
+    if (p1 > 0.0 && p2 > 0.0) {
+        const double p = std::sqrt(p2 / 6.0);
+        double m[3][3];
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) m[i][j] = (s[i][j] - (i == j ? q : 0.0)) / p;
+        const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                           m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+        const double phi = std::acos(std::min(1.0, std::max(-1.0, 0.5 * det))) / 3.0;
+        lo = q + 2.0 * p * std::cos(phi + 2.0943951023931953);
+        hi = q + 2.0 * p * std::cos(phi);
+    }
+    rmin = std::sqrt(std::max(lo, 0.0)); rmax = std::sqrt(std::max(hi, 0.0));
+}
+
+// A sphere or ellipsoid stays outside every tree, and has no `culled` bound, when the error of its
+// own test can pass its margin for a ray that starts OM_SPHERE_REACH away.  From the
+// operation order of sphere_root, with u = 2^-24, L = |w2l (o - c)| <= D / rmin and a = |w2l d|^2:
+// half_b = lo . ld carries 3u L sqrt(a), half_b^2 7u a L^2, c = lo . lo - 1 4u L^2, a 3u a, a c 8u a L^2,
+// the subtraction u a L^2: disc / a is known to 16u L^2, so `disc >= 0` accepts a local distance from
+// the centre of up to 1 + 8u L^2, which is at most 8u D^2 rmax / rmin^2 in the world.  (The roundings
+// of lo and ld themselves only shift the ray, by a few u (C + D): the gradient of disc in lo is
+// -2a times the perpendicular part of lo, of length 1 at the silhouette.)  The margin is the smallest
+// the primitive gets: its box's, 1e-3 (1 + extent) + 1e-5 |coord| on the tightest axis, or its
+// bounding sphere's, 1e-3 (1 + rmax) + 1e-5 |c|.  A non-finite transform compares false and stays.
+bool thin_sphere(const Mat4& l2w) {
+    double rmin, rmax;
+    semi_axes(l2w, rmin, rmax);
+    double h[3], mag = 0.0, cn = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        const double a0 = l2w.r[i].e[0], a1 = l2w.r[i].e[1], a2 = l2w.r[i].e[2], c = l2w.r[i].e[3];
+        h[i] = std::sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+        mag = std::max(mag, std::max(std::fabs(c - h[i]), std::fabs(c + h[i])));
+        cn += c * c;
+    }
+    double margin = 1e-3 * (1.0 + rmax) + 1e-5 * std::sqrt(cn);
+    for (int i = 0; i < 3; ++i) margin = std::min(margin, 1e-3 * (1.0 + 2.0 * h[i]) + 1e-5 * mag);
+    const double u = 5.9604644775390625e-8, D = OM_SPHERE_REACH;
+    return 8.0 * u * D * D * rmax / (rmin * rmin) > margin;
+}
+
 void build_bvh(const om_world& w, FrozenWorld& fw) {
     Builder b;
     std::vector<uint32_t> always;
     const double kHuge = 100.0;  // a bound larger than this is tested outside the BVH
-    auto add = [&](const Box& box, uint32_t gi) {
+    auto add = [&](const Box& box, uint32_t gi, bool thin = false) {
         double ext = 0.0;
         for (int i = 0; i < 3; ++i) ext = std::max(ext, box.hi[i] - box.lo[i]);
-        if (ext > 2.0 * kHuge) { always.push_back(gi); return; }
+        if (ext > 2.0 * kHuge || thin) { always.push_back(gi); return; }
         Item it; it.b = box; it.gi = gi;
         for (int i = 0; i < 3; ++i) it.c[i] = 0.5 * (box.lo[i] + box.hi[i]);
         b.items.push_back(it);
     };
-    for (size_t i = 0; i < w.spheres.size(); ++i) add(affine_box(w.spheres[i].l2w, -1.0), fw.offsets[K_SPHERE] + (uint32_t)i);
+    for (size_t i = 0; i < w.spheres.size(); ++i) add(affine_box(w.spheres[i].l2w, -1.0), fw.offsets[K_SPHERE] + (uint32_t)i, thin_sphere(w.spheres[i].l2w));
     for (size_t i = 0; i < w.cubes.size(); ++i) add(affine_box(w.cubes[i].l2w, 0.5), fw.offsets[K_CUBE] + (uint32_t)i);
     for (size_t i = 0; i < w.triangles.size(); ++i) add(bary_box(w.triangles[i], false), fw.offsets[K_TRI] + (uint32_t)i);
     for (size_t i = 0; i < w.planes.size(); ++i) always.push_back(fw.offsets[K_PLANE] + (uint32_t)i);
@@ -236,15 +289,15 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
     Builder b;
     std::vector<uint32_t> always;
     const double kHuge = 100.0;
-    auto add = [&](const Box& box, uint32_t gi) {
+    auto add = [&](const Box& box, uint32_t gi, bool thin = false) {
         double ext = 0.0;
         for (int i = 0; i < 3; ++i) ext = std::max(ext, box.hi[i] - box.lo[i]);
-        if (ext > 2.0 * kHuge) { always.push_back(gi); return; }
+        if (ext > 2.0 * kHuge || thin) { always.push_back(gi); return; }
         Item it; it.b = box; it.gi = gi;
         for (int i = 0; i < 3; ++i) it.c[i] = 0.5 * (box.lo[i] + box.hi[i]);
         b.items.push_back(it);
     };
-    for (size_t i = 0; i < w.spheres.size(); ++i) add(affine_box(w.spheres[i].l2w, -1.0), fw.offsets[K_SPHERE] + (uint32_t)i);
+    for (size_t i = 0; i < w.spheres.size(); ++i) add(affine_box(w.spheres[i].l2w, -1.0), fw.offsets[K_SPHERE] + (uint32_t)i, thin_sphere(w.spheres[i].l2w));
     for (size_t i = 0; i < w.cubes.size(); ++i) add(affine_box(w.cubes[i].l2w, 0.5), fw.offsets[K_CUBE] + (uint32_t)i);
     // Triangles and parallelograms: from OM_BARY_TREE_MIN of them on, the ones with
     // a finite frozen record and a finite box go to the SAH builder beside the spheres and cubes

@@ -288,6 +288,8 @@ struct om_ctx {
     int primary_lists = OM_PRIMARY_LISTS_AUTO;
     DevBuf tile_off, tile_idx, tile_tnear;
     bool tiles_valid = false, tiles_use = false;
+    float root_box[6] = {0, 0, 0, 0, 0, 0};   // box of the bounded primitives (the global BVH's root); have_root: there is one
+    bool have_root = false;
     om_camera tiles_cam{};
     uint32_t tiles_w = 0, tiles_h = 0;
     uint64_t tiles_gen = 0;
@@ -521,6 +523,19 @@ om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_
     if (pipeline == OM_PIPELINE_AUTO) pipeline = OM_PIPELINE_WAVEFRONT;
     int mode = c->kernel;
     if (mode == OM_KERNEL_AUTO) mode = OM_KERNEL_BVH2;
+    // A camera beyond the reach of the slab test (OM_SLAB_REACH, far_origin in om_wavefront.hip: with d its
+    // largest axis distance from the box of the bounded primitives and R the box's diagonal,
+    // 2 sqrt(3) d + R > 8192) renders with the reference loop: out there the slab test is no finer than the
+    // box inflation.  Decided per call on the host; no other frame runs anything else.
+    if (c->have_root) {
+        const float* b = c->root_box;
+        float d = 0.0f, r2 = 0.0f;
+        for (int i = 0; i < 3; ++i) {
+            d = std::max(d, std::max(b[i] - cam->origin[i], cam->origin[i] - b[3 + i]));
+            r2 += (b[3 + i] - b[i]) * (b[3 + i] - b[i]);
+        }
+        if (3.4641016f * d + std::sqrt(r2) > OM_SLAB_REACH) mode = OM_KERNEL_BRUTE;
+    }
     if (pipeline == OM_PIPELINE_WAVEFRONT) {
         omw::Launch L;
         L.S = c->scene; L.C = C; L.P = P;
@@ -681,6 +696,8 @@ om_status om_upload_world(om_ctx* c, const om_world* w) {
     S.off_msph = fw.offsets[5]; S.off_mbox = fw.offsets[6]; S.off_mtor = fw.offsets[7];
     S.off_msdf = fw.offsets[om::K_MSDF]; S.n_total = fw.offsets[om::K_N];
     S.n_bvh_nodes = (uint32_t)fw.bvh.size();
+    c->have_root = !fw.bvh.empty();
+    if (c->have_root) for (int i = 0; i < 3; ++i) { c->root_box[i] = fw.bvh[0].lo[i]; c->root_box[3 + i] = fw.bvh[0].hi[i]; }
     S.n_always = (uint32_t)fw.always.size();
     S.n_snodes = (uint32_t)fw.snodes.size(); S.n_srecs = (uint32_t)fw.srecs.size(); S.n_always2 = (uint32_t)fw.always2.size();
     S.lds_bytes = plan.lds_bytes;

@@ -46,8 +46,12 @@ __device__ __forceinline__ float slab_far(float x0, float x1, float y0, float y1
 
 // Inverse direction component for the conservative slab tests only (never an output value):
 // the hardware reciprocal (1 ulp) instead of the correctly rounded division, ~10 VALU each.
-// Boxes are inflated by 1e-3*(1+extent) and the t window is loosened by 1e-4 relative, far
-// beyond its error; the component is kept >= 1e-20 in magnitude, so the result is finite.
+// Boxes are inflated by 1e-3*(1+extent) + 1e-5*|coord| and the t window is loosened by 1e-4
+// relative: beyond the reciprocal's error (1 ulp of each slab value) at the scene scale, where the
+// margin also covers the exact tests' own rounding.  Both margins are absolute and the error of
+// Sphere::hit grows with (origin distance)^2 / radius: DESIGN.md §5.3 gives the domain in which
+// the culls are conservative and what happens outside it.  The component is kept >= 1e-20 in
+// magnitude, so the result is finite.
 __device__ __forceinline__ float inv_dir(float c) {
     const float k = fabsf(c) > 1e-20f ? c : copysignf(1e-20f, c);
     return __builtin_amdgcn_rcpf(k);
@@ -326,7 +330,8 @@ __device__ __forceinline__ void test_leaf_code(const OmSceneDev& S, const OmAffi
 // order: box hit -> next node (internal) or the leaf's records then `skip`; miss ->
 // `skip`.  No per-lane stack (no scratch), one 32-B node read per step.  The box test
 // only decides which exact tests run, so it may use FMA (it never touches output bits):
-// boxes are inflated far beyond its rounding, the direction is kept away from 0 so
+// boxes are inflated beyond its rounding at the scene scale (not for every ray
+// origin and primitive size), the direction is kept away from 0 so
 // every slab value is finite, and NaN compares fall through to "visit".
 // NODES/RECS point into LDS (staged once per workgroup) or into global memory.
 template <class Wk>

@@ -168,3 +168,20 @@
 #ifndef OM_BARY_TREE_MIN
 #define OM_BARY_TREE_MIN 16
 #endif
+// Ray queries: the reach of the slab test (far_origin in om_wavefront.hip).  With the
+// origin d (largest axis distance, 0 inside) from the box of the bounded primitives, of diagonal R,
+// the origin is at most sqrt(3) d from the box and a root inside it at most t = sqrt(3) d + R away;
+// the slab test (reciprocal to 1 ulp, one fma per plane) places a plane to within 2u (|o - box| + t),
+// u = 2^-24, beyond what the 1e-5 |coord| term of the inflation carries.  That stays below the
+// inflation's floor of 1e-3 while 2 sqrt(3) d + R <= 1e-3 / 2u = 8389; a ray with more takes the
+// reference loop -- every ray of a world whose bounded primitives span more than that.
+#ifndef OM_SLAB_REACH
+#define OM_SLAB_REACH 8192.0f
+#endif
+// The distance of a ray origin from a sphere or ellipsoid up to which its box must cover the worst
+// case of Sphere::hit's rounding (thin_sphere in om_bvh.cpp): the reference scene's own camera distance,
+// 13.4, rounded up to a power of two.  A sphere whose margin cannot do that stays outside the trees.
+// Beyond it the culls hold for the typical, not the worst, rounding.
+#ifndef OM_SPHERE_REACH
+#define OM_SPHERE_REACH 16.0
+#endif

@@ -953,6 +953,18 @@ void k_tail(OmSceneDev S, OmParamsDev P, Seg G, Queue in, const uint32_t* __rest
 // for: t_hi = tmax * 1.0001 + 1e-3 >= tmax for every tmax that can hold a root >= tmin >= 0 (+inf
 // included), and a window with tmin > tmax accepts nothing in either form.
 __device__ __forceinline__ bool window_edge(float tmin, float tmax) { return !(tmin >= 0.0f) || tmax != tmax; }
+// A query ray beyond the reach of the slab test takes the reference loop as well: with the origin d
+// (largest axis distance) from the box of the bounded primitives (the root of the global BVH, which
+// every kernel's upload holds), of diagonal R, the slab test's own rounding reaches the inflation's
+// floor of 1e-3 once 2 sqrt(3) d + R passes OM_SLAB_REACH (om_tuning.h).  A NaN origin
+// compares false and keeps the non-finite path.
+__device__ __forceinline__ bool far_origin(const OmSceneDev& S, F3 o) {
+    if (S.n_bvh_nodes == 0) return false;
+    const OmBvhNode N = S.bvh[0];
+    const float dx = fmaxf(N.lo[0] - o.x, o.x - N.hi[0]), dy = fmaxf(N.lo[1] - o.y, o.y - N.hi[1]), dz = fmaxf(N.lo[2] - o.z, o.z - N.hi[2]);
+    const float ex = N.hi[0] - N.lo[0], ey = N.hi[1] - N.lo[1], ez = N.hi[2] - N.lo[2];
+    return 3.4641016f * fmaxf(fmaxf(dx, fmaxf(dy, dz)), 0.0f) + sqrtf(ex * ex + ey * ey + ez * ez) > OM_SLAB_REACH;
+}
 __device__ __forceinline__ void load_query_window(const om_ray_window* __restrict__ win, uint64_t i, float& tmin, float& tmax) {
     if (((uintptr_t)win & 7u) == 0u) {
         const float2* w2 = (const float2*)(win + i);
@@ -1022,7 +1034,7 @@ __device__ __forceinline__ void query_rays(const OmSceneDev& S, const OmParamsDe
         constexpr bool kShortcut = T0 == TR_BVH2_LDS || T0 == TR_BVH2_GLOBAL || T0 == TR_BVH4_LDS || T0 == TR_BVH4_GLOBAL || T0 == TR_BVH2_WIDE;
         float tmin = P.tmin, tmax = P.tmax;
         if (WIN) load_query_window(windows, i, tmin, tmax);
-        if ((kShortcut && !isfinite(o.x + o.y + o.z + d.x + d.y + d.z)) || (WIN && window_edge(tmin, tmax))) {
+        if ((kShortcut && !isfinite(o.x + o.y + o.z + d.x + d.y + d.z)) || (WIN && window_edge(tmin, tmax)) || far_origin(S, o)) {
             closest = tmax;
             best = traced_brute<false>(S, o, d, tmin, closest, w);
         } else {
@@ -1088,7 +1100,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_occluded(OmSceneDev S, O
             if (windows) load_query_window(windows, i, tmin, tmax);
             float closest = tmax;
             int best;
-            if (!isfinite(o.x + o.y + o.z + d.x + d.y + d.z) || window_edge(tmin, tmax)) best = traced_brute<false>(S, o, d, tmin, closest, w);
+            if (!isfinite(o.x + o.y + o.z + d.x + d.y + d.z) || window_edge(tmin, tmax) || far_origin(S, o)) best = traced_brute<false>(S, o, d, tmin, closest, w);
             else best = trace_traced<TR>(S, T, o, d, tmin, closest, w);
             if (MARCH && best < 0) {
                 float tm;

@@ -129,7 +129,8 @@ double sigma_max(const Mat4& l2w) {
     return std::sqrt(std::max(ev, 0.0));
 }
 
-// Conservative bound: radius inflated well beyond f32 rounding.
+// Bound for the `culled` pre-test: radius inflated beyond f32 rounding at the
+// scene scale; like the tree boxes it is not conservative for far ray origins (§5.3; a thin sphere gets none).
 OmBound make_bound(const Mat4& l2w, double local_radius) {
     OmBound b;
     const double cx = l2w.r[0].e[3], cy = l2w.r[1].e[3], cz = l2w.r[2].e[3];
@@ -187,6 +188,7 @@ void om_world::freeze(FrozenWorld& fw) const {
     for (size_t i = 0; i < spheres.size(); ++i) {
         pack_affine(spheres[i], fw.sph_test[i], fw.sph_hit[i]);
         fw.sph_bound[i] = make_bound(spheres[i].l2w, 1.0);
+        if (thin_sphere(spheres[i].l2w)) fw.sph_bound[i].r = INFINITY;   // no pre-test: every comparison with it is false (§5.3)
         put_mat(fw.offsets[K_SPHERE] + (uint32_t)i, spheres[i].mat);
     }
     fw.cube_test.resize(cubes.size()); fw.cube_hit.resize(cubes.size()); fw.cube_bound.resize(cubes.size());

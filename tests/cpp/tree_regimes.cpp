@@ -62,12 +62,15 @@ void cluster_world(om_world* w, uint32_t per, uint32_t side) {
             }
 }
 
-// 4000 spheres on a line, spacing and radius growing geometrically (x_i = 1e-3 * 1.004^i, the
-// radius a quarter of the gap): a SAH split peels the far end off level after level
+// 4000 spheres on a line, spacing and radius growing geometrically (x_i = 250 * 1.0015^i, the
+// radius a quarter of the gap): a SAH split peels the far end off level after level.  The radii run
+// from 0.094 to 38, inside what the builder keeps in its trees (a sphere whose margin cannot cover
+// its test's rounding from 16 away, and a bound above 200, both stay outside them);
+// the line spans e^6 where it once spanned e^16 (ratio 1.004 from x = 1e-3), so the peeling is milder.
 void line_world(om_world* w) {
-    double x = 1e-3;
+    double x = 250.0;
     for (uint32_t i = 0; i < 4000u; ++i) {
-        const double gap = x * 0.004;
+        const double gap = x * 0.0015;
         const float c[3] = {(float)x, 0.f, 0.f};
         const om_material m = palette(i);
         EXPECT(om_world_add_sphere_radius(w, c, (float)(0.25 * gap), &m) == OM_OK);

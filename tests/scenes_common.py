@@ -259,3 +259,33 @@ def user_sdf_zoo(om, O, torus_as_program=False):
     cam = om.Camera.new((2.6, 1.4, 3.2), (0., 0.4, -0.2), (0., 1., 0.), 40., 1.5, 0.02, 4.)
     ocam = O.camera((2.6, 1.4, 3.2), (0., 0.4, -0.2), (0., 1., 0.), 40., 1.5, 0.02, 4.)
     return w, ow, cam, ocam
+
+
+# ---- ray-query helpers shared by the GPU query tests and the CPU-only scale tests
+def _unit(d):
+    d = np.asarray(d, dtype=F)
+    n = np.sqrt((d * d).sum(axis=1, dtype=F), dtype=F)
+    return (d / n[:, None]).astype(F)
+
+
+def pinhole_rays(cam, w=48, h=32):
+    """Centre rays of a w x h frame, no lens offset: origin -> llc + u*horizontal + v*vertical."""
+    r = cam.raw
+    org, hor, ver, llc = (np.array(list(x), dtype=F) for x in (r.origin, r.horizontal, r.vertical, r.lower_left_corner))
+    j, i = np.meshgrid(np.arange(h, dtype=F), np.arange(w, dtype=F), indexing="ij")
+    u = ((i.reshape(-1) + F(0.5)) / F(w)).astype(F)
+    v = (F(1.0) - (j.reshape(-1) + F(0.5)) / F(h)).astype(F)
+    d = _unit(llc[None, :] + u[:, None] * hor[None, :] + v[:, None] * ver[None, :] - org[None, :])
+    return np.concatenate([np.broadcast_to(org, d.shape), d], axis=1).astype(F)
+
+
+def oracle_hits(om, ow, rays, tmin=0.001, tmax=100.0):
+    """oracle.World.hit per ray -> HIT_DTYPE records (None -> the miss record)."""
+    out = np.zeros(len(rays), dtype=om.HIT_DTYPE)
+    out["t"] = np.inf
+    for k, r in enumerate(rays):
+        h = ow.hit(r[:3], r[3:], tmin, tmax)
+        if h is not None:
+            v, oid = h
+            out[k] = (v[0], v[1:4], v[4:7], oid)
+    return out

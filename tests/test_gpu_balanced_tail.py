@@ -188,6 +188,7 @@ def test_sharded_pixel_list(frames):
             pix = shard.tile_pixels(W, H, r, 3)
             dpix = torch.from_numpy(pix.view(np.int32)).cuda()
             st = torch.zeros(pix.size * 40, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()       # torch's fill and copy are queued on its stream, the render on the ctx's own
             L.check(L.lib.om_render_device_pixels(fz.ctx, C.byref(cam.raw), C.byref(p), C.c_void_p(st.data_ptr()),
                                                   C.c_void_p(dpix.data_ptr()), pix.size, None), fz.ctx)
             torch.cuda.synchronize()

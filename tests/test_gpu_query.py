@@ -27,7 +27,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from scenes_common import REGIME_WORLDS, kitchen_sink, tie_scene
+from scenes_common import REGIME_WORLDS, _unit, kitchen_sink, oracle_hits, pinhole_rays, tie_scene  # noqa: F401  (re-exported)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,35 +40,6 @@ SBVH_WORLDS = ["g15", "g16"]
 SMALL_WORLDS = ("g0x", "g0")
 MIN_DISTINCT, MIN_HIT_SHARE = 226, 0.459          # 80 % of the smallest measured values (docstring)
 MIN_HIT_SHARE_SMALL = 0.3768                      # the same for g0x / g0 (smallest 0.471)
-
-
-def _unit(d):
-    d = np.asarray(d, dtype=F)
-    n = np.sqrt((d * d).sum(axis=1, dtype=F), dtype=F)
-    return (d / n[:, None]).astype(F)
-
-
-def pinhole_rays(cam, w=W, h=H):
-    """Centre rays of a w x h frame, no lens offset: origin -> llc + u*horizontal + v*vertical."""
-    r = cam.raw
-    org, hor, ver, llc = (np.array(list(x), dtype=F) for x in (r.origin, r.horizontal, r.vertical, r.lower_left_corner))
-    j, i = np.meshgrid(np.arange(h, dtype=F), np.arange(w, dtype=F), indexing="ij")
-    u = ((i.reshape(-1) + F(0.5)) / F(w)).astype(F)
-    v = (F(1.0) - (j.reshape(-1) + F(0.5)) / F(h)).astype(F)
-    d = _unit(llc[None, :] + u[:, None] * hor[None, :] + v[:, None] * ver[None, :] - org[None, :])
-    return np.concatenate([np.broadcast_to(org, d.shape), d], axis=1).astype(F)
-
-
-def oracle_hits(om, ow, rays, tmin=0.001, tmax=100.0):
-    """oracle.World.hit per ray -> HIT_DTYPE records (None -> the miss record)."""
-    out = np.zeros(len(rays), dtype=om.HIT_DTYPE)
-    out["t"] = np.inf
-    for k, r in enumerate(rays):
-        h = ow.hit(r[:3], r[3:], tmin, tmax)
-        if h is not None:
-            v, oid = h
-            out[k] = (v[0], v[1:4], v[4:7], oid)
-    return out
 
 
 def ray_sets(om, ow, cam, lo, hi, seed=RAY_SEED, tmin=0.001, tmax=100.0):

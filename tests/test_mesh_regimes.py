@@ -46,7 +46,9 @@ def test_every_world_is_reported_with_its_primitives(report, om, oracle):
 
 def test_ico2_bvh2_in_lds_with_direct_codes(report):
     r = report["ico2"]
-    assert r["triangles"] == 320 and r["rec_bary"] == 320 and r["rec_other"] == 4, "ground outside, 3 ellipsoids + cube inside"
+    # (the small ellipsoid, semi-axes 0.03 .. 0.05, is a thin sphere: outside the trees like the ground)
+    assert r["triangles"] == 320 and r["rec_bary"] == 320 and r["rec_other"] == 3, "ground and the small ellipsoid outside, 2 ellipsoids + cube inside"
+    assert r["always2"] == 2
     assert r["always_tri_boxed"] == 0 and r["always_tri_unbounded"] == 0
     assert r["b2_ok"] == 1 and r["b2_lds_bytes"] != 0 and r["b2_direct"] == 1
     assert r["b4_ok"] == 1 and r["b4_lds_bytes"] != 0 and r["lds_bytes"] != 0, "BVH4 and the megakernel's SBVH staged too"
@@ -76,9 +78,9 @@ def test_leaves_mix_kinds(report):
 def test_below_the_threshold_keeps_the_always2_layout(report):
     r = report["below"]
     assert r["triangles"] == MC.OM_BARY_TREE_MIN - 1
-    assert r["rec_bary"] == 0 and r["srecs"] == r["rec_other"] == 4, "no barycentric record in srecs"
+    assert r["rec_bary"] == 0 and r["srecs"] == r["rec_other"] == 3, "no barycentric record in srecs (2 ellipsoids + cube)"
     assert r["always_tri_boxed"] == r["triangles"] and r["always_tri_unbounded"] == 0, "all of them in always2 with boxes"
-    assert r["always2"] == r["triangles"] + 1, "the ground and the triangles"
+    assert r["always2"] == r["triangles"] + 2, "the ground, the small ellipsoid (a thin sphere) and the triangles"
 
 
 def test_degenerate_triangle_stays_outside_unbounded(report):

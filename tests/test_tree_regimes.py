@@ -153,7 +153,8 @@ def test_largest_admitted_lds_request_fits_a_workgroup(report):
 def test_builder_depth_bound_holds_on_a_geometric_line(report):
     """4000 spheres on a line with geometrically growing gaps and radii: SAH peels the far end off
     level after level, the builder's switch to median splits at depth 10 must keep the tree within
-    the 24-entry lane stack -- otherwise the wavefront drops to the scratch-stack BVH."""
+    the 24-entry lane stack -- otherwise the wavefront drops to the scratch-stack BVH.  (The line spans
+    e^6, radii 0.094 to 38: what the builder keeps in its trees; it spanned e^16 before thin spheres left them.)"""
     _, w = report
     ln = w["line4000"]
     assert ln["srecs"] == 4000
