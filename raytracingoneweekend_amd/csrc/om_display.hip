@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kB) void k_maxes_final(Part* __restrict__ parts, ui
     if (threadIdx.x == 0) parts[nparts] = sh[0];
 }
 
-// ---- per-pixel views: MODE_NORMAL 0, MODE_SHOW_SAMPLES 1, MODE_SHOW_DEPTH 3, MODE_SHOW_IDS 5
+// ---- per-pixel views (main.rs display modes): NORMAL 0, SHOW_SAMPLES 1, SHOW_DEPTH 3, SHOW_IDS 5
 template <int MODE>
 __global__ __launch_bounds__(kB) void k_view(const om_pixel_stats* __restrict__ st, uint32_t npx, const Part* __restrict__ mx,
                                              uint8_t* __restrict__ rgb) {

@@ -1,5 +1,5 @@
 // om_internal.h — what other translation units of libottomarcher.so need from an om_ctx
-// (defined in om_render.hip); not part of the C-ABI.
+// (defined in om_render.hip, the C API); not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -7,9 +7,17 @@
 // (what the winner needs to build its HitRecord).  Global primitive index gi
 // follows the type order; obj_id = gi + 1 (0 = sky).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
+#include "om_tuning.h"
+
 #define OM_ALIGN16 __attribute__((aligned(16)))
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define OM_HD __host__ __device__
+#else
+#define OM_HD
+#endif
 
 // Affine primitive (Sphere traced.rs:13-19, Cube traced.rs:229-235).
 // w2l rows 0..2 (row-major 3x4); dz[i] = w2l[i][3] * 0.0f — the w-term of
@@ -277,3 +285,33 @@ struct OmParamsDev {
 // after them and is not cleared by om_reset_counters
 enum { OMC_SAMPLES = 0, OMC_SEGMENTS, OMC_PRIM_TESTS, OMC_PRE_TESTS, OMC_MARCH, OMC_CREDITED, OMC_N };
 enum { OMC_PROGRESS = OMC_N, OMC_SLOTS };
+
+// Closest-hit kernel variants (omw::Launch::trace_mode, the kernels' TR / MODE template argument; the
+// values are part of the mangled kernel names the profile tools read).  The megakernel runs the first
+// six (its TR_BVH2_LDS also reads the nodes through L2); the wavefront and the ray queries all but TR_SBVH_LDS.
+enum { TR_BRUTE = 1, TR_CULLED = 2, TR_BVH = 3, TR_SBVH_LDS = 4, TR_SBVH_GLOBAL = 5, TR_BVH2_LDS = 6, TR_BVH2_GLOBAL = 7,
+       TR_BVH4_LDS = 8, TR_BVH4_GLOBAL = 9,
+       // the BVH2 with 32-bit child codes and a u32 lane stack (OmBvh2NodeW): trees past
+       // the 15-bit codes, and any non-empty BVH2 under OM_KERNEL_BVH2W.  Always with TR_BARY: one set
+       // of instantiations, whose leaf test handles sphere and cube records by tag
+       TR_BVH2_WIDE = 10,
+       // flag on a tree variant (TR_SBVH_GLOBAL, TR_BVH2_*, TR_BVH4_*): the world's leaves hold triangles /
+       // parallelograms (OmSceneDev::n_srec_bary), so the kernels are the instantiations
+       // whose leaf test carries the barycentric case (WorkT's BARY); every other world runs the
+       // instantiations without the flag, the code it ran before meshes
+       TR_BARY = 16 };
+constexpr int tr_base(int tr) { return tr & (TR_BARY - 1); }      // the variant without the flag
+constexpr bool tr_bary(int tr) { return (tr & TR_BARY) != 0; }
+
+// the world holds marched primitives: the kernels' MARCH instantiations
+OM_HD inline bool has_marched(const OmSceneDev& S) { return (S.n_msph + S.n_mbox + S.n_mtor + S.n_msdf) != 0u; }
+// segments a path may run (ray_color's depth, render_thread.rs:142; at least one)
+OM_HD inline uint32_t depth_cap(const OmParamsDev& P) { return P.max_depth > 1u ? P.max_depth : 1u; }
+// A ray origin beyond the reach of the slab test (OM_SLAB_REACH, om_tuning.h): with d the
+// origin's largest axis distance from the box [lo, hi] of the bounded primitives (0 inside) and R the
+// box's diagonal, 2 sqrt(3) d + R > OM_SLAB_REACH.  A NaN origin compares false.
+OM_HD inline bool beyond_slab_reach(const float* lo, const float* hi, float ox, float oy, float oz) {
+    const float dx = fmaxf(lo[0] - ox, ox - hi[0]), dy = fmaxf(lo[1] - oy, oy - hi[1]), dz = fmaxf(lo[2] - oz, oz - hi[2]);
+    const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
+    return 3.4641016f * fmaxf(fmaxf(dx, fmaxf(dy, dz)), 0.0f) + sqrtf(ex * ex + ey * ey + ez * ez) > OM_SLAB_REACH;
+}

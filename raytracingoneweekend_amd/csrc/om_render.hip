@@ -1,19 +1,7 @@
-// om_render.hip — the hot path on MI355X (gfx950): per-pixel ray_color
-// integrator (render_thread.rs:105-202) with closest-hit over the frozen world
-// (hits.rs:270-365), as one persistent-path megakernel.
-//
-// Execution model: one lane owns one pixel for the whole call
-// and walks that pixel's samples in order (so Stats::add sees samples in the
-// reference's order, bit for bit).  The bounce recursion is flattened into a
-// segment loop with path REGENERATION: when a lane's path ends, the same loop
-// iteration starts that pixel's next sample, so every active lane runs the
-// closest-hit query of some live ray each iteration — the SIMD-utilisation
-// benefit of wavefront compaction without the HBM ray queues.  A wave owns an
-// 8x8 pixel tile for ray coherence.  Scene records are read at wave-uniform
-// addresses (scalar loads) and stay L2/LDS resident.
-//
-// The wide BVH2 (32-bit child codes) is the wavefront's and the ray queries':
-// the megakernel keeps MODE_BVH for a tree past the 15-bit codes and for OM_KERNEL_BVH2W.
+// om_render.hip — the C API of libottomarcher.so (include/ottomarcher.h), host side: the context,
+// world upload, render and ray-query entry points, counters, timing, progress and display.  The
+// kernels are elsewhere: a render call goes to the wavefront (om_wavefront.hip) or the megakernel
+// (om_megakernel.hip), a ray query to om_wavefront.hip, a view to om_display.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,213 +32,6 @@ static_assert(sizeof(OmBvh2NodeW) == sizeof(OmBvh2NodeH) && sizeof(om_tree_info)
 
 namespace {
 
-constexpr int kBlock = 256;
-
-// ---------------------------------------------------------------------------
-// closest hit over the traced primitives
-// ---------------------------------------------------------------------------
-enum { MODE_BRUTE = 1, MODE_CULLED = 2, MODE_BVH = 3, MODE_SBVH_LDS = 4, MODE_SBVH_GLOBAL = 5, MODE_BVH2 = 6 };
-constexpr int kStack2 = 24;                    // BVH2 lane-stack bound (om_upload_world checks the depth)
-constexpr int kBlockLds = 512;
-
-}  // namespace
-
-#include "om_trace.h"
-
-namespace {
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-extern __shared__ __attribute__((aligned(16))) uint4 om_lds[];
-
-// MARCH is a compile-time split (as in the wavefront): traced-only scenes do not carry
-// the sphere-tracing code's registers.  BARY likewise (SBVH / BVH2 modes): worlds whose leaves
-// hold triangles / parallelograms run the leaf test with the barycentric case.
-template <int MODE, int BLOCK, bool COUNT, bool MARCH, bool BARY = false>
-__global__ __launch_bounds__(BLOCK, (BLOCK >= 512 ? 4 : 1)) void render_kernel(OmSceneDev S, OmCamDev C, OmParamsDev P,
-                                                       const float2* __restrict__ jitter,
-                                                       om_pixel_stats* __restrict__ stats,
-                                                       const uint32_t* __restrict__ pixel_list,
-                                                       unsigned long long* __restrict__ counters) {
-    if (MODE == MODE_SBVH_LDS) {
-        // stage the stackless BVH + its records once per workgroup (uint4 chunks)
-        const uint32_t nn = S.n_snodes * 2u, nr = S.n_srecs * 4u;
-        const uint4* sn = (const uint4*)S.snodes;
-        const uint4* sr = (const uint4*)S.srecs;
-        for (uint32_t i = threadIdx.x; i < nn; i += BLOCK) om_lds[i] = sn[i];
-        for (uint32_t i = threadIdx.x; i < nr; i += BLOCK) om_lds[nn + i] = sr[i];
-        __syncthreads();
-    }
-    const OmSkipNode* lds_nodes = (const OmSkipNode*)om_lds;
-    const OmAffineTest* lds_recs = (const OmAffineTest*)(om_lds + S.n_snodes * 2u);
-    // BVH2: [lane stack][nodes][leaf table] in LDS (nodes through L2 when they exceed the budget)
-    uint16_t* b2_stk = (uint16_t*)om_lds + threadIdx.x;
-    const OmBvh2Node* b2_nodes = S.b2nodes;
-    const uint32_t* b2_leaves = S.b2leaves;
-    if (MODE == MODE_BVH2 && S.b2_lds_bytes) {
-        uint4* dst = om_lds + (BLOCK * S.b2_stack * 2u) / 16u;
-        const uint32_t nn = S.n_b2nodes * (uint32_t)(sizeof(OmBvh2Node) / 16u);
-        const uint4* sn = (const uint4*)S.b2nodes;
-        for (uint32_t i = threadIdx.x; i < nn; i += BLOCK) dst[i] = sn[i];
-        uint32_t* ldst = (uint32_t*)(dst + nn);
-        for (uint32_t i = threadIdx.x; i < S.n_b2leaves; i += BLOCK) ldst[i] = S.b2leaves[i];
-        __syncthreads();
-        b2_nodes = (const OmBvh2Node*)dst;
-        b2_leaves = ldst;
-    }
-    const uint32_t tid = blockIdx.x * BLOCK + threadIdx.x;
-    uint32_t pixel, slot;
-    bool valid;
-    if (pixel_list) {
-        valid = tid < P.n_pixels;
-        pixel = valid ? pixel_list[tid] : 0u;
-        slot = tid;
-    } else {
-        const uint32_t wave = tid >> 6, lane = tid & 63u;
-        const uint32_t tx = wave % P.tiles_x, ty = wave / P.tiles_x;
-        const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
-        valid = px < P.width && py < P.height;
-        pixel = py * P.width + px;
-        slot = pixel;
-    }
-    PixelState st;
-    if (valid) {
-        const om_pixel_stats in = stats[slot];
-        st.bloom = in.bloom; st.sx = in.sum[0]; st.sy = in.sum[1]; st.sz = in.sum[2]; st.n = in.n;
-        st.avg_depth = in.avg_depth; st.bad = in.bad_avgs;
-        st.rgbf = (uint32_t)in.color[0] | ((uint32_t)in.color[1] << 8) | ((uint32_t)in.color[2] << 16) | ((uint32_t)in.flags << 24);
-    } else {
-        st.bloom = 0; st.sx = st.sy = st.sz = 0.0f; st.n = 0; st.avg_depth = 0.0f; st.bad = 0; st.rgbf = 0;
-    }
-    const uint32_t line = valid ? pixel / P.width : 0u;
-    const float j_f = (float)line, i_f = (float)(pixel - P.width * line);
-    const uint32_t depth_cap = P.max_depth > 1u ? P.max_depth : 1u;
-
-    uint32_t todo = valid ? P.sample_count : 0u;
-    bool live = false;
-    F3 o = f3(0, 0, 0), d = f3(0, 0, 0), cur = f3(1, 1, 1);
-    Rng g; g.s = 0; g.k = 0;
-    uint32_t seg = 0, first_id = 0;
-    float depthf = 0.0f;
-    WorkT<COUNT, false, BARY> w;
-    uint32_t n_samples = 0, n_segments = 0, credited = 0;
-
-    for (;;) {
-        if (!live && todo > 0u) {
-            if ((P.adaptive && (st.rgbf & 0x01000000u)) || st.n >= P.spp_total) {
-                todo = 0u;
-            } else {
-                // render_thread.rs:183-192 + Camera::get_ray camera.rs:60-65
-                const uint32_t s = st.n;
-                g = path_rng(P.skey, pixel, s);
-                const float2 jt = jitter[s];
-                const float i_rand = (g.next() + jt.x) / 2.0f;
-                const float j_rand = (g.next() + jt.y) / 2.0f;
-                const float u = (i_f + i_rand) / P.wf_m1;
-                const float v = 1.0f - (j_f + j_rand) / P.hf_m1;
-                float dx, dy;
-                for (;;) {                                                     // rand_in_unit_disc vec3.rs:108-113
-                    dx = g.range(-1.0f, 1.0f);
-                    dy = g.range(-1.0f, 1.0f);
-                    if (dx * dx + dy * dy < 1.0f) break;
-                }
-                const float rlx = dx * C.lens_radius, rly = dy * C.lens_radius;
-                const F3 off = f3(C.u[0] * rlx + C.v[0] * rly, C.u[1] * rlx + C.v[1] * rly, C.u[2] * rlx + C.v[2] * rly);
-                // uv_to_dir . (u, v, 0, 1): ((H*u + V*v) + 0*0) + D*1
-                const F3 dir = f3((C.horizontal[0] * u + C.vertical[0] * v) + 0.0f * 0.0f + C.llc_minus_origin[0],
-                                  (C.horizontal[1] * u + C.vertical[1] * v) + 0.0f * 0.0f + C.llc_minus_origin[1],
-                                  (C.horizontal[2] * u + C.vertical[2] * v) + 0.0f * 0.0f + C.llc_minus_origin[2]);
-                o = add(ld3(C.origin), off);
-                d = unit(unit(sub(dir, off)));                                 // camera.rs:64 + ray.rs:12
-                cur = f3(1.0f, 1.0f, 1.0f);
-                seg = 0; live = true; todo--;
-            }
-        }
-        if (__ballot(live) == 0ull) break;
-        if (!live) continue;
-
-        // ---- one segment: handle_hit(world.hit(ray)) render_thread.rs:105-126
-        if (COUNT) n_segments++;
-        float closest = P.tmax;
-        int best;
-        if (MODE == MODE_SBVH_LDS) best = traced_sbvh(S, lds_nodes, lds_recs, o, d, P.tmin, closest, w);
-        else if (MODE == MODE_SBVH_GLOBAL) best = traced_sbvh(S, S.snodes, S.srecs, o, d, P.tmin, closest, w);
-        else if (MODE == MODE_BVH) best = traced_bvh(S, o, d, P.tmin, closest, w);
-        else if (MODE == MODE_BVH2) best = traced_bvh2<kStack2, BLOCK>(S, b2_nodes, b2_leaves, S.srecs, b2_stk, o, d, P.tmin, closest, w);
-        else best = traced_brute<MODE == MODE_CULLED>(S, o, d, P.tmin, closest, w);
-        if (MARCH) {
-            float tm;
-            const int mg = march(S, o, d, P.tmin, P.tmax, closest, P.march_steps, tm, w);
-            if (mg >= 0) { best = mg; closest = tm; }
-        }
-        float seg_depth; uint32_t seg_id;
-        if (best >= 0) {
-            F3 point, normal;
-            finalize<MARCH>(S, best, o, d, P.tmin, closest, point, normal);
-            F3 nd, att;
-            scatter(S.mats[best], d, normal, g, nd, att);
-            cur = mul(cur, att);
-            o = point; d = unit(nd);
-            seg_depth = closest; seg_id = (uint32_t)best + 1u;
-        } else {
-            const float t = 0.5f * (d.y + 1.0f);                               // render_thread.rs:118-120
-            cur = mul(cur, f3((1.0f - t) + 0.5f * t, (1.0f - t) + 0.7f * t, (1.0f - t) + 1.0f * t));
-            seg_depth = INFINITY; seg_id = 0u;
-        }
-        bool finished = false;
-        F3 result = cur;
-        float rdepth = 0.0f; uint32_t rid = 0;
-        if (seg == 0u) {
-            depthf = seg_depth; first_id = seg_id;
-            if (isinf(seg_depth)) { finished = true; rdepth = INFINITY; rid = 0u; }     // :133-135
-        } else if (isinf(seg_depth)) {
-            finished = true; rdepth = depthf; rid = first_id;                       // :138-140
-        }
-        if (!finished && seg + 1u >= depth_cap) {                              // :142  -Color::ZERO
-            finished = true; result = f3(-0.0f, -0.0f, -0.0f); rdepth = depthf; rid = first_id;
-        }
-        seg++;
-        if (finished) {
-            const bool done = stats_add(st, result, rdepth, S.bloom[rid]);
-            if (COUNT) n_samples++;
-            credited += ((done && P.adaptive) ? (P.spp_total - st.n) : 0u) + 1u;     // :196-198
-            live = false;
-        }
-    }
-
-    if (valid) {
-        om_pixel_stats out;
-        out.bloom = st.bloom; out.sum[0] = st.sx; out.sum[1] = st.sy; out.sum[2] = st.sz; out.n = st.n;
-        out.avg_depth = st.avg_depth; out.bad_avgs = st.bad;
-        out.color[0] = (uint8_t)(st.rgbf & 0xFFu); out.color[1] = (uint8_t)((st.rgbf >> 8) & 0xFFu);
-        out.color[2] = (uint8_t)((st.rgbf >> 16) & 0xFFu); out.flags = (uint8_t)(st.rgbf >> 24); out.reserved = 0u;
-        stats[slot] = out;
-    }
-    if (COUNT) {
-        const uint32_t c0 = wave_sum(n_samples), c1 = wave_sum(n_segments), c2 = wave_sum(w.prim), c3 = wave_sum(w.pre),
-                       c4 = wave_sum(w.march), c5 = wave_sum(credited);
-        if ((threadIdx.x & 63u) == 0u) {
-            atomicAdd(&counters[OMC_SAMPLES], (unsigned long long)c0);
-            atomicAdd(&counters[OMC_SEGMENTS], (unsigned long long)c1);
-            atomicAdd(&counters[OMC_PRIM_TESTS], (unsigned long long)c2);
-            atomicAdd(&counters[OMC_PRE_TESTS], (unsigned long long)c3);
-            atomicAdd(&counters[OMC_MARCH], (unsigned long long)c4);
-            atomicAdd(&counters[OMC_CREDITED], (unsigned long long)c5);
-        }
-    }
-    if (P.progress) {                                                          // live samples_atom (om_progress)
-        const uint32_t c = wave_sum(credited);
-        if ((threadIdx.x & 63u) == 0u && c) atomicAdd(&counters[OMC_PROGRESS], (unsigned long long)c);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------------
 thread_local std::string g_err;
 
 struct DevBuf {
@@ -403,34 +184,6 @@ om_status validate(om_ctx* c, const om_camera* cam, const om_render_params* p) {
     return OM_OK;
 }
 
-template <int MODE, int BLOCK>
-void go(bool count, uint64_t threads, uint32_t lds, hipStream_t stream, const OmSceneDev& S, const OmCamDev& C,
-        const OmParamsDev& P, const float2* jt, om_pixel_stats* st, const uint32_t* px, unsigned long long* ctr) {
-    const uint32_t blocks = (uint32_t)((threads + BLOCK - 1) / BLOCK);
-    const bool march = (S.n_msph + S.n_mbox + S.n_mtor + S.n_msdf) != 0u;
-    if constexpr (MODE == MODE_SBVH_LDS || MODE == MODE_SBVH_GLOBAL || MODE == MODE_BVH2) {
-        if (S.n_srec_bary) {                                   // triangles / parallelograms in the leaves
-            if (count && march)
-                hipLaunchKernelGGL((render_kernel<MODE, BLOCK, true, true, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
-            else if (count)
-                hipLaunchKernelGGL((render_kernel<MODE, BLOCK, true, false, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
-            else if (march)
-                hipLaunchKernelGGL((render_kernel<MODE, BLOCK, false, true, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
-            else
-                hipLaunchKernelGGL((render_kernel<MODE, BLOCK, false, false, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
-            return;
-        }
-    }
-    if (count && march)
-        hipLaunchKernelGGL((render_kernel<MODE, BLOCK, true, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
-    else if (count)
-        hipLaunchKernelGGL((render_kernel<MODE, BLOCK, true, false>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
-    else if (march)
-        hipLaunchKernelGGL((render_kernel<MODE, BLOCK, false, true>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
-    else
-        hipLaunchKernelGGL((render_kernel<MODE, BLOCK, false, false>), dim3(blocks), dim3(BLOCK), lds, stream, S, C, P, jt, st, px, ctr);
-}
-
 // Primary-ray candidate lists for (camera, frame, world), rebuilt only when one changes.
 // AUTO uses them when a pixel sees <= 12 candidates on average (a primary BVH2 traversal
 // costs ~11 node visits + 3.5 exact tests); S-traced at 1080p sees 3.2 (max 14 per tile).
@@ -468,17 +221,37 @@ om_status ensure_tile_lists(om_ctx* c, const om_camera* cam, uint32_t W, uint32_
 
 // omw::Launch::trace_mode of a resolved (non-AUTO) OM_KERNEL_* choice
 int wf_trace_mode(int mode) {
-    return mode == OM_KERNEL_BRUTE ? MODE_BRUTE : mode == OM_KERNEL_CULLED ? MODE_CULLED
-         : mode == OM_KERNEL_BVH ? MODE_BVH : mode == OM_KERNEL_BVH2 ? 6
-         : mode == OM_KERNEL_BVH4 ? 8 : mode == OM_KERNEL_BVH2W ? 10 : MODE_SBVH_LDS;
+    return mode == OM_KERNEL_BRUTE ? TR_BRUTE : mode == OM_KERNEL_CULLED ? TR_CULLED
+         : mode == OM_KERNEL_BVH ? TR_BVH : mode == OM_KERNEL_BVH2 ? TR_BVH2_LDS
+         : mode == OM_KERNEL_BVH4 ? TR_BVH4_LDS : mode == OM_KERNEL_BVH2W ? TR_BVH2_WIDE : TR_SBVH_LDS;
+}
+
+// The wavefront's pixel list of a full frame: 8x8 tiles in row-major tile order, lanes row-major
+// inside a tile; rebuilt when the frame size changes.
+om_status ensure_frame_list(om_ctx* c, uint32_t W, uint32_t H, hipStream_t stream) {
+    if (c->frame_w == W && c->frame_h == H && c->frame_list.p) return OM_OK;
+    std::vector<uint32_t> lst;
+    lst.reserve((size_t)W * H);
+    const uint32_t tx = (W + 7u) / 8u, ty = (H + 7u) / 8u;
+    for (uint32_t t = 0; t < tx * ty; ++t)
+        for (uint32_t l = 0; l < 64u; ++l) {
+            const uint32_t px = (t % tx) * 8u + (l & 7u), py = (t / tx) * 8u + (l >> 3);
+            if (px < W && py < H) lst.push_back(py * W + px);
+        }
+    om_status s = ensure(c, c->frame_list, lst.size() * 4);
+    if (s != OM_OK) return s;
+    OM_HIP(c, hipMemcpyAsync(c->frame_list.p, lst.data(), lst.size() * 4, hipMemcpyHostToDevice, stream));
+    OM_HIP(c, hipStreamSynchronize(stream));
+    c->frame_w = W; c->frame_h = H;
+    return OM_OK;
 }
 
 om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_pixel_stats* dev_stats,
                  const uint32_t* dev_pixels, uint32_t n_pixels, hipStream_t stream) {
     // samples_per_pixel = 0: render()'s pass loop never runs (render_thread.rs:176), Stats untouched
     if (p->spp_total == 0 || p->sample_count == 0) return OM_OK;
-    const float2* jitter = nullptr;
-    om_status s = prepare_jitter(c, p->seed, p->spp_total, &jitter);
+    omw::Launch L;
+    om_status s = prepare_jitter(c, p->seed, p->spp_total, &L.jitter);
     if (s) return s;
     if (!c->counters.p) {
         s = ensure(c, c->counters, OMC_SLOTS * sizeof(unsigned long long));
@@ -486,14 +259,14 @@ om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_
         OM_HIP(c, hipMemsetAsync(c->counters.p, 0, OMC_SLOTS * sizeof(unsigned long long), stream));
     }
     c->last_stream = stream;
-    OmCamDev C;
+    OmCamDev& C = L.C;
     for (int i = 0; i < 3; ++i) {
         C.origin[i] = cam->origin[i]; C.horizontal[i] = cam->horizontal[i]; C.vertical[i] = cam->vertical[i];
         C.llc_minus_origin[i] = cam->lower_left_corner[i] - cam->origin[i];          // camera.rs:72
         C.u[i] = cam->u_of_plane[i]; C.v[i] = cam->v_of_plane[i];
     }
     C.lens_radius = cam->lens_radius;
-    OmParamsDev P;
+    OmParamsDev& P = L.P;
     P.width = p->width; P.height = p->height; P.spp_total = p->spp_total; P.sample_count = p->sample_count;
     P.max_depth = p->max_depth; P.march_steps = p->march_steps; P.adaptive = p->adaptive ? 1u : 0u;
     P.tmin = p->tmin; P.tmax = p->tmax;
@@ -505,50 +278,37 @@ om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_
     P.skey = z ^ (z >> 31);
     P.tiles_x = (p->width + 7u) / 8u;
     P.progress = c->progress_host ? 1u : 0u;
-    uint64_t threads;
-    if (dev_pixels) {
-        P.n_pixels = n_pixels;
-        threads = n_pixels;
-    } else {
-        const uint64_t tiles = (uint64_t)P.tiles_x * ((p->height + 7u) / 8u);
-        P.n_pixels = p->width * p->height;
-        threads = tiles * 64u;
-    }
-    if (threads == 0) return OM_OK;
-    int pipeline = c->pipeline;
+    P.n_pixels = dev_pixels ? n_pixels : p->width * p->height;
+    if (P.n_pixels == 0) return OM_OK;
+    int mode = c->kernel;
+    if (mode == OM_KERNEL_AUTO) mode = OM_KERNEL_BVH2;
+    // A camera beyond the reach of the slab test (beyond_slab_reach, the rule of far_origin in
+    // om_wavefront.hip, against the box of the bounded primitives) renders with the reference loop:
+    // out there the slab test is no finer than the box inflation.  Decided per call
+    // on the host; no other frame runs anything else.
+    if (c->have_root && beyond_slab_reach(c->root_box, c->root_box + 3, cam->origin[0], cam->origin[1], cam->origin[2]))
+        mode = OM_KERNEL_BRUTE;
+    L.S = c->scene;
+    L.stats = dev_stats;
+    L.pixels = dev_pixels; L.n_pixels = P.n_pixels; L.stats_by_pixel = !dev_pixels;
+    L.counters = (unsigned long long*)c->counters.p;
+    L.count = c->count_work;
+    L.trace_mode = wf_trace_mode(mode);
+    L.tail_bounce = c->tail_bounce;
+    L.streams = c->wf_streams;
+    L.ad_batches = c->ad_batches; L.ad_paths_log2 = c->ad_paths_log2;
+    L.timer = &c->timer;
+    L.tile_off = nullptr; L.tile_idx = nullptr; L.tile_tnear = nullptr;
+    L.progress_host = c->progress_host;
+    std::string err;
+    hipError_t e;
     // AUTO: the wavefront, the faster pipeline on every measured config since r04:
     // C1 6100 vs 3142 Msamples/s, C2 with one stream 2377 vs 1180-1202 (r04_ad), C2 adaptive 2939 vs
     // 1041 credited (16-sample calls), C1 adaptive 3466 vs 2832 (16-sample calls), 4199 vs 3388 (64),
     // all counting build; production build, C1 adaptive 64 spp in one call: 7171 vs 3392-3507 (r04_q7).
-    if (pipeline == OM_PIPELINE_AUTO) pipeline = OM_PIPELINE_WAVEFRONT;
-    int mode = c->kernel;
-    if (mode == OM_KERNEL_AUTO) mode = OM_KERNEL_BVH2;
-    // A camera beyond the reach of the slab test (OM_SLAB_REACH, far_origin in om_wavefront.hip: with d its
-    // largest axis distance from the box of the bounded primitives and R the box's diagonal,
-    // 2 sqrt(3) d + R > 8192) renders with the reference loop: out there the slab test is no finer than the
-    // box inflation.  Decided per call on the host; no other frame runs anything else.
-    if (c->have_root) {
-        const float* b = c->root_box;
-        float d = 0.0f, r2 = 0.0f;
-        for (int i = 0; i < 3; ++i) {
-            d = std::max(d, std::max(b[i] - cam->origin[i], cam->origin[i] - b[3 + i]));
-            r2 += (b[3 + i] - b[i]) * (b[3 + i] - b[i]);
-        }
-        if (3.4641016f * d + std::sqrt(r2) > OM_SLAB_REACH) mode = OM_KERNEL_BRUTE;
-    }
-    if (pipeline == OM_PIPELINE_WAVEFRONT) {
-        omw::Launch L;
-        L.S = c->scene; L.C = C; L.P = P;
-        L.jitter = jitter;
-        L.stats = dev_stats;
-        L.counters = (unsigned long long*)c->counters.p;
-        L.count = c->count_work;
-        L.tail_bounce = c->tail_bounce;
-        L.streams = c->wf_streams;
-        L.ad_batches = c->ad_batches; L.ad_paths_log2 = c->ad_paths_log2;
-        L.timer = &c->timer;
-        L.tile_off = nullptr; L.tile_idx = nullptr; L.tile_tnear = nullptr;
-        L.progress_host = c->progress_host;
+    if (c->pipeline == OM_PIPELINE_MEGAKERNEL) {
+        e = omw::render_megakernel(L, stream, err);
+    } else {
         // (a tree past the 15-bit codes has n_b2nodes 0: its primary rays traverse, and om_tiles.cpp
         // lists at most 65 535 records anyway; OM_KERNEL_BVH2W takes the lists like OM_KERNEL_BVH2)
         if ((mode == OM_KERNEL_BVH2 && c->scene.n_b2nodes) || (mode == OM_KERNEL_BVH2W && c->scene.n_b2wnodes)) {
@@ -558,59 +318,13 @@ om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_
                 L.tile_tnear = (const float*)c->tile_tnear.p;
             }
         }
-        L.trace_mode = wf_trace_mode(mode);
-        if (dev_pixels) {
-            L.pixels = dev_pixels; L.n_pixels = n_pixels; L.stats_by_pixel = false;
-        } else {
-            if (c->frame_w != p->width || c->frame_h != p->height || !c->frame_list.p) {
-                // 8x8 tiles in row-major tile order, lanes row-major inside a tile
-                std::vector<uint32_t> lst;
-                lst.reserve((size_t)p->width * p->height);
-                const uint32_t tx = (p->width + 7u) / 8u, ty = (p->height + 7u) / 8u;
-                for (uint32_t t = 0; t < tx * ty; ++t)
-                    for (uint32_t l = 0; l < 64u; ++l) {
-                        const uint32_t px = (t % tx) * 8u + (l & 7u), py = (t / tx) * 8u + (l >> 3);
-                        if (px < p->width && py < p->height) lst.push_back(py * p->width + px);
-                    }
-                if ((s = ensure(c, c->frame_list, lst.size() * 4)) != OM_OK) return s;
-                OM_HIP(c, hipMemcpyAsync(c->frame_list.p, lst.data(), lst.size() * 4, hipMemcpyHostToDevice, stream));
-                OM_HIP(c, hipStreamSynchronize(stream));
-                c->frame_w = p->width; c->frame_h = p->height;
-            }
-            L.pixels = (const uint32_t*)c->frame_list.p; L.n_pixels = p->width * p->height; L.stats_by_pixel = true;
+        if (!dev_pixels) {
+            if ((s = ensure_frame_list(c, p->width, p->height, stream)) != OM_OK) return s;
+            L.pixels = (const uint32_t*)c->frame_list.p;
         }
-        std::string err;
-        const hipError_t e = omw::render(c->wf, L, stream, err);
-        if (e != hipSuccess) return set_err(c, OM_ERR_DEVICE, err + ": " + hipGetErrorString(e));
-        return OM_OK;
+        e = omw::render(c->wf, L, stream, err);
     }
-    const float2* jt = jitter;
-    unsigned long long* ctr = (unsigned long long*)c->counters.p;
-    const bool count = c->count_work;
-    const int mk_ti = c->timer.begin(stream);
-    if (mode == OM_KERNEL_SBVH) {
-        if (c->scene.lds_bytes)
-            go<MODE_SBVH_LDS, kBlockLds>(count, threads, c->scene.lds_bytes, stream, c->scene, C, P, jt, dev_stats, dev_pixels, ctr);
-        else
-            go<MODE_SBVH_GLOBAL, kBlockLds>(count, threads, 0, stream, c->scene, C, P, jt, dev_stats, dev_pixels, ctr);
-    } else if (mode == OM_KERNEL_BRUTE) {
-        go<MODE_BRUTE, kBlock>(count, threads, 0, stream, c->scene, C, P, jt, dev_stats, dev_pixels, ctr);
-    } else if (mode == OM_KERNEL_CULLED) {
-        go<MODE_CULLED, kBlock>(count, threads, 0, stream, c->scene, C, P, jt, dev_stats, dev_pixels, ctr);
-    } else if ((mode == OM_KERNEL_BVH2 || mode == OM_KERNEL_BVH4) && c->scene.n_b2nodes) {
-        const uint32_t lds = kBlock * c->scene.b2_stack * 2u + c->scene.b2_lds_bytes;
-        go<MODE_BVH2, kBlock>(count, threads, lds, stream, c->scene, C, P, jt, dev_stats, dev_pixels, ctr);
-    } else if ((mode == OM_KERNEL_BVH2 || mode == OM_KERNEL_BVH4) && c->scene.n_bvh_nodes <= 1u) {
-        // empty BVH2 and at most one leaf in the old BVH (marched-only worlds): the reference
-        // loop, without MODE_BVH's scratch-memory stack
-        go<MODE_BRUTE, kBlock>(count, threads, 0, stream, c->scene, C, P, jt, dev_stats, dev_pixels, ctr);
-    } else {
-        go<MODE_BVH, kBlock>(count, threads, 0, stream, c->scene, C, P, jt, dev_stats, dev_pixels, ctr);
-    }
-    c->timer.end(mk_ti, OM_KT_MEGAKERNEL, stream);
-    OM_HIP(c, hipGetLastError());
-    if (c->progress_host)   // one launch per call: the word advances when it ends
-        OM_HIP(c, hipMemcpyAsync(c->progress_host, ctr + OMC_PROGRESS, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    if (e != hipSuccess) return set_err(c, OM_ERR_DEVICE, err + ": " + hipGetErrorString(e));
     return OM_OK;
 }
 

@@ -1,6 +1,6 @@
-// om_trace.h — closest-hit query over the frozen world (hits.rs:270-365) and the
-// HitRecord of the winner; shared by the megakernel (om_render.hip) and the
-// wavefront pipeline (om_wavefront.hip).
+// om_trace.h — closest-hit query over the frozen world (hits.rs:270-365), the HitRecord of
+// the winner, the camera ray and the counter flush; shared by the megakernel
+// (om_megakernel.hip) and the wavefront pipeline (om_wavefront.hip).
 #pragma once
 #include "om_device.h"
 #include "om_layout.h"
@@ -683,6 +683,18 @@ __device__ __forceinline__ void gen_camera_ray(const OmCamDev& C, const OmParams
                       (C.horizontal[2] * u + C.vertical[2] * v) + 0.0f * 0.0f + C.llc_minus_origin[2]);
     o = add(ld3(C.origin), off);
     d = unit(unit(sub(dir, off)));                                 // camera.rs:64 + ray.rs:12
+}
+
+// Work counters: the wave's sum of a lane value, and its add to a counter slot (one atomic per wave).
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// (`first`: the lane is its wave's first; a kernel in which threadIdx.x is live anyway passes its own test)
+__device__ __forceinline__ void flush_counter(unsigned long long* ctr, int slot, uint32_t v, bool first = __lane_id() == 0) {
+    v = wave_sum32(v);
+    if (first && v) atomicAdd(&ctr[slot], (unsigned long long)v);
 }
 
 }  // namespace omd

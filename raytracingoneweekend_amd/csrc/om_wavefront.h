@@ -1,9 +1,11 @@
-// om_wavefront.h — host interface of the wavefront pipeline.
+// om_wavefront.h — host interface of the two render pipelines: the wavefront and the
+// megakernel (§5.1), and of the ray queries.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ottomarcher.h"
@@ -77,12 +79,12 @@ struct Launch {
     OmParamsDev P;
     const float2* jitter;
     om_pixel_stats* stats;
-    const uint32_t* pixels;      // device list of row-major pixel indices (tile order)
+    const uint32_t* pixels;      // device list of row-major pixel indices (tile order); megakernel: null = the full frame
     uint32_t n_pixels;
     bool stats_by_pixel;         // stats[pixel] (full frame) instead of stats[k]
     unsigned long long* counters;
     bool count;
-    int trace_mode;              // closest-hit kernel variant (om_render.hip MODE_*)
+    int trace_mode;              // the ctx's kernel choice as a TR_* value (om_layout.h), before the world decides
     uint32_t tail_bounce;        // first bounce run by the persistent tail kernel (0 = default)
     uint32_t streams;            // batches in flight (queue sets, streams), 1 = serial, <= kMaxSets
     uint32_t ad_batches;         // adaptive calls: batches per stream per call (0 = OM_WF_ADAPTIVE_BATCHES)
@@ -96,6 +98,18 @@ struct Launch {
 
 // Renders P.sample_count samples of every listed pixel; returns 0 or a HIP error text.
 hipError_t render(Buffers& B, const Launch& L, hipStream_t stream, std::string& err);
+// The same as one render_kernel launch (om_megakernel.hip); of L it reads neither the wavefront's
+// schedule knobs nor the tile lists.
+hipError_t render_megakernel(const Launch& L, hipStream_t stream, std::string& err);
+
+// f(std::bool_constant<b[0]>{}, std::bool_constant<b[1]>{}, ...): runtime flags as template arguments.
+// f is instantiated for every combination; it leaves out the ones never launched with if constexpr.
+template <size_t N, class F, class... C>
+void with_flags(const bool (&b)[N], F&& f, C... c) {
+    if constexpr (sizeof...(C) == N) f(c...);
+    else if (b[sizeof...(C)]) with_flags(b, f, c..., std::true_type{});
+    else with_flags(b, f, c..., std::false_type{});
+}
 
 // One batch of ray queries: closest-hit (om_hit_rays*_device) when `occluded` is
 // null, any-hit (om_occluded_rays_device, §5.16) otherwise.

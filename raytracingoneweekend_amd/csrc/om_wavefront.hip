@@ -61,19 +61,6 @@ void Buffers::release() {
 namespace {
 
 constexpr uint32_t kNoSample = 0xFFFFFFFFu;
-enum { TR_BRUTE = 1, TR_CULLED = 2, TR_BVH = 3, TR_SBVH_LDS = 4, TR_SBVH_GLOBAL = 5, TR_BVH2_LDS = 6, TR_BVH2_GLOBAL = 7,
-       TR_BVH4_LDS = 8, TR_BVH4_GLOBAL = 9,
-       // the BVH2 with 32-bit child codes and a u32 lane stack (OmBvh2NodeW): trees past
-       // the 15-bit codes, and any non-empty BVH2 under OM_KERNEL_BVH2W.  Always with TR_BARY: one set
-       // of instantiations, whose leaf test handles sphere and cube records by tag
-       TR_BVH2_WIDE = 10,
-       // flag on a tree variant (TR_SBVH_GLOBAL, TR_BVH2_*, TR_BVH4_*): the world's leaves hold triangles /
-       // parallelograms (OmSceneDev::n_srec_bary), so the kernels are the instantiations
-       // whose leaf test carries the barycentric case (WorkT's BARY); every other world runs the
-       // instantiations without the flag, the code it ran before meshes
-       TR_BARY = 16 };
-constexpr int tr_base(int tr) { return tr & (TR_BARY - 1); }      // the variant without the flag
-constexpr bool tr_bary(int tr) { return (tr & TR_BARY) != 0; }
 #define OM_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(OM_WF_WAVES, OM_WF_WAVES)))   // occupancy request (waves per SIMD)
 constexpr int kBlk = OM_WF_BLOCK;                                 // workgroup = one queue segment
 constexpr int kStackDepth = 24;                                   // BVH2 per-lane LDS stack bound (entries)
@@ -150,16 +137,6 @@ __host__ __device__ constexpr bool exact_view_built() { return TR == TR_BRUTE ||
 __host__ __device__ inline Deal batch_deal(uint64_t paths, uint32_t nseg) { return make_deal(paths, nseg, OM_WF_DEAL_BLOCKS); }
 
 extern __shared__ __attribute__((aligned(16))) uint4 wf_lds[];
-
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ void flush_counter(unsigned long long* ctr, int slot, uint32_t v) {
-    v = wave_sum32(v);
-    if (__lane_id() == 0 && v) atomicAdd(&ctr[slot], (unsigned long long)v);
-}
 
 struct Seg {
     uint32_t nseg;    // segments (= bounce workgroups)
@@ -371,7 +348,7 @@ __device__ __forceinline__ int trace(const OmSceneDev& S, const OmParamsDev& P, 
 // segment.  Returns true when the path continues (p advanced to the next segment);
 // otherwise the sample's (colour, depth, id) is written to its result slot.
 template <bool MARCH, bool USER = MARCH>
-__device__ __forceinline__ bool shade_path(const OmSceneDev& S, const OmParamsDev& P, uint32_t depth_cap, Path& p,
+__device__ __forceinline__ bool shade_path(const OmSceneDev& S, const OmParamsDev& P, uint32_t cap, Path& p,
                                            float closest, int best, float4* __restrict__ res,
                                            uint32_t* __restrict__ res_id) {
     float seg_depth; uint32_t seg_id;
@@ -397,7 +374,7 @@ __device__ __forceinline__ bool shade_path(const OmSceneDev& S, const OmParamsDe
     } else if (isinf(seg_depth)) {
         finished = true; rdepth = p.depthf; rid = p.first_id;                            // :138-140
     }
-    if (!finished && p.seg + 1u >= depth_cap) {                                          // :142 -Color::ZERO
+    if (!finished && p.seg + 1u >= cap) {                                          // :142 -Color::ZERO
         finished = true; result = f3(-0.0f, -0.0f, -0.0f); rdepth = p.depthf; rid = p.first_id;
     }
     if (finished) {
@@ -490,7 +467,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
     if (threadIdx.x == 0) { q_next = kBlk / 64u; q_out = 0u; }
     __syncthreads();
     const Tracer T = HIT ? Tracer{} : stage_scene<TR>(S);
-    const uint32_t depth_cap = P.max_depth > 1u ? P.max_depth : 1u;
+    const uint32_t cap = depth_cap(P);
     WorkT<COUNT, false, tr_bary(TR)> w;
     uint32_t segs = 0;
     const uint32_t lane = __lane_id();
@@ -552,7 +529,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
                 } else if (!(listed && sg == 0u)) {
                     best = trace<TR, MARCH>(S, P, T, p.o, p.d, closest, w);
                 }
-                keep = shade_path<MARCH, USER>(S, P, depth_cap, p, closest, best, res, res_id);
+                keep = shade_path<MARCH, USER>(S, P, cap, p, closest, best, res, res_id);
                 if (COUNT) segs++;
             }
             if (!FUSE || sg == 1u || __ballot(keep) == 0) break;   // wave-uniform
@@ -733,7 +710,7 @@ __device__ __forceinline__ uint32_t tail_march_lanes(const OmSceneDev& S, const 
                                                      const Src& src, uint32_t total, uint32_t& next,
                                                      float4* __restrict__ res, uint32_t* __restrict__ res_id, Wk& w) {
     const uint32_t lane = __lane_id();
-    const uint32_t depth_cap = P.max_depth > 1u ? P.max_depth : 1u;
+    const uint32_t cap = depth_cap(P);
     uint32_t idx = threadIdx.x, segs = 0, iters = 0;
     bool have = idx < total, dry = !have, marching = false, act = false;
     // The march steps need only the ray; the rest of the path (throughput, first hit, segment,
@@ -785,7 +762,7 @@ __device__ __forceinline__ uint32_t tail_march_lanes(const OmSceneDev& S, const 
         if (ended && (OM_WF_TAIL_SHADE <= 1 || __popcll(em) >= OM_WF_TAIL_SHADE || am == 0)) {
             if (COUNT) segs++;
             unpark();
-            if (shade_path<true, M::USER>(S, P, depth_cap, p, closest, best, res, res_id)) begin();
+            if (shade_path<true, M::USER>(S, P, cap, p, closest, best, res, res_id)) begin();
             else have = false;
         }
         const uint64_t want = __ballot(!have && !dry), busy = __ballot(have);
@@ -887,7 +864,7 @@ void k_tail(OmSceneDev S, OmParamsDev P, Seg G, Queue in, const uint32_t* __rest
     if (threadIdx.x == 0) pre[G.nseg] = total;
     __syncthreads();
     const Tracer T = stage_scene<TR>(S);
-    const uint32_t depth_cap = P.max_depth > 1u ? P.max_depth : 1u;
+    const uint32_t cap = depth_cap(P);
     const TailSrc src{in, pre, 0u, G.nseg, G.segcap};
     WorkT<COUNT, false, tr_bary(TR)> w;
     uint32_t segs = 0;
@@ -903,7 +880,7 @@ void k_tail(OmSceneDev S, OmParamsDev P, Seg G, Queue in, const uint32_t* __rest
             float closest;
             const int best = trace<TR, false>(S, P, T, p.o, p.d, closest, w);
             if (COUNT) segs++;
-            have = shade_path<false>(S, P, depth_cap, p, closest, best, res, res_id);
+            have = shade_path<false>(S, P, cap, p, closest, best, res, res_id);
         }
         if (more) {                                           // the ended lanes' next paths at once
             const uint64_t want = __ballot(!have);
@@ -961,9 +938,7 @@ __device__ __forceinline__ bool window_edge(float tmin, float tmax) { return !(t
 __device__ __forceinline__ bool far_origin(const OmSceneDev& S, F3 o) {
     if (S.n_bvh_nodes == 0) return false;
     const OmBvhNode N = S.bvh[0];
-    const float dx = fmaxf(N.lo[0] - o.x, o.x - N.hi[0]), dy = fmaxf(N.lo[1] - o.y, o.y - N.hi[1]), dz = fmaxf(N.lo[2] - o.z, o.z - N.hi[2]);
-    const float ex = N.hi[0] - N.lo[0], ey = N.hi[1] - N.lo[1], ez = N.hi[2] - N.lo[2];
-    return 3.4641016f * fmaxf(fmaxf(dx, fmaxf(dy, dz)), 0.0f) + sqrtf(ex * ex + ey * ey + ez * ez) > OM_SLAB_REACH;
+    return beyond_slab_reach(N.lo, N.hi, o.x, o.y, o.z);
 }
 __device__ __forceinline__ void load_query_window(const om_ray_window* __restrict__ win, uint64_t i, float& tmin, float& tmax) {
     if (((uintptr_t)win & 7u) == 0u) {
@@ -1299,25 +1274,24 @@ inline uint32_t count_rows(uint32_t depth_cap) { return std::max<uint32_t>(depth
 
 // One batch: bounce 0 .. tail_at-1 as per-bounce launches, then the tail launch, all on `st`;
 // returns the number of bounce-family launches.
-template <int TR, bool COUNT, bool MARCH>
-uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Gen& R, uint32_t depth_cap,
-                   uint32_t tail_at, uint32_t lds, uint32_t tail_grid) {
+// EXACT (marched worlds, where exact_view_built<TR>()): the marched set has C2's shape and no user
+// object (OmMSdf), so the march kernels take MarchedC2Lds and the shade leaves the SDF programs out.
+template <int TR, bool COUNT, bool MARCH, bool EXACT>
+uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Gen& R, uint32_t tail_at, uint32_t lds,
+                   uint32_t tail_grid) {
+    constexpr int VIEW = EXACT && exact_view_built<TR>() ? MV_EXACT_C2_LDS : MV_ARRAYS;
     Timer& tm = *L.timer;
     const bool each = tm.mode == 1;
     uint32_t launches = 0;
-    const bool exact = MARCH && L.S.n_msdf == 0u && MarchedC2Lds::matches(L.S.n_msph, L.S.n_mbox, L.S.n_mtor);
+    const uint32_t cap = depth_cap(L.P);
     // the traced tail's claim counter: the word behind the set's per-bounce counts
-    uint32_t* const tail_next = B.counts + (size_t)count_rows(depth_cap) * G.nseg;
+    uint32_t* const tail_next = B.counts + (size_t)count_rows(cap) * G.nseg;
     auto tail = [&](const Queue& in, const uint32_t* cin) {
         const int ti = each ? tm.begin(st) : -1;
         if constexpr (MARCH) {
             const uint32_t grid = (G.nseg + kTailSpb - 1u) / kTailSpb;
-            if (exact && exact_view_built<TR>())
-                hipLaunchKernelGGL((k_tail_march<TR, COUNT, exact_view_built<TR>() ? MV_EXACT_C2_LDS : MV_ARRAYS>), dim3(grid),
-                                   dim3(kBlk), lds, st, L.S, L.P, G, in, cin, B.res, B.res_id, L.counters);
-            else
-                hipLaunchKernelGGL((k_tail_march<TR, COUNT>), dim3(grid), dim3(kBlk), lds, st, L.S, L.P, G, in, cin,
-                                   B.res, B.res_id, L.counters);
+            hipLaunchKernelGGL((k_tail_march<TR, COUNT, VIEW>), dim3(grid), dim3(kBlk), lds, st, L.S, L.P, G, in, cin,
+                               B.res, B.res_id, L.counters);
         } else {
             hipLaunchKernelGGL((k_tail<TR, COUNT>), dim3(tail_grid), dim3(kBlk), tail_lds(lds, G.nseg), st, L.S, L.P, G, in, cin,
                                tail_pre_off(lds), tail_next, B.res, B.res_id, L.counters);
@@ -1335,27 +1309,19 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
             tm.end(ti, OM_KT_BOUNCE0, st);
             ++launches;
         }
-        for (uint32_t bounce = 0; bounce < depth_cap; ++bounce) {
+        for (uint32_t bounce = 0; bounce < cap; ++bounce) {
             const Queue in = queue(B, bounce & 1u), out = queue(B, (bounce + 1u) & 1u);
             const uint32_t* cin = B.counts + (size_t)bounce * G.nseg;
             if (bounce >= tail_at) return tail(in, cin);   // (tail_at 0: k_raygen's camera paths too)
             uint32_t* cout = B.counts + (size_t)(bounce + 1u) * G.nseg;
             const int kc = bounce == 0 ? OM_KT_BOUNCE0 : OM_KT_BOUNCE;
             int ti = each ? tm.begin(st) : -1;
-            if (exact && exact_view_built<TR>())
-                hipLaunchKernelGGL((k_march<TR, COUNT, exact_view_built<TR>() ? MV_EXACT_C2_LDS : MV_ARRAYS>), dim3(G.nseg),
-                                   dim3(kBlk), lds, st, L.S, L.P, G, in, cin, B.hit, L.counters);
-            else
-                hipLaunchKernelGGL((k_march<TR, COUNT, MV_ARRAYS>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, in, cin,
-                                   B.hit, L.counters);
+            hipLaunchKernelGGL((k_march<TR, COUNT, VIEW>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, in, cin, B.hit,
+                               L.counters);
             tm.end(ti, kc, st);
             ti = each ? tm.begin(st) : -1;
-            if (exact && exact_view_built<TR>())                       // no user objects (OmMSdf) in the world
-                hipLaunchKernelGGL((k_bounce<TR, COUNT, MARCH, false, true, false>), dim3(G.nseg), dim3(kBlk), 0, st, L.S, L.P, G,
-                                   R, in, cin, out, cout, B.res, B.res_id, L.counters, (const float2*)B.hit, (uint32_t*)nullptr);
-            else
-                hipLaunchKernelGGL((k_bounce<TR, COUNT, MARCH, false, true>), dim3(G.nseg), dim3(kBlk), 0, st, L.S, L.P, G, R, in,
-                                   cin, out, cout, B.res, B.res_id, L.counters, (const float2*)B.hit, (uint32_t*)nullptr);
+            hipLaunchKernelGGL((k_bounce<TR, COUNT, MARCH, false, true, !EXACT>), dim3(G.nseg), dim3(kBlk), 0, st, L.S, L.P, G, R,
+                               in, cin, out, cout, B.res, B.res_id, L.counters, (const float2*)B.hit, (uint32_t*)nullptr);
             tm.end(ti, kc, st);
             launches += 2u;
         }
@@ -1363,7 +1329,7 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
     } else {
     // (fused first launch: bounces 0 and 1, its out queue is bounce 2's; the first queue the tail or a
     // per-bounce launch can read is the one that launch wrote, whatever tail_at asks for)
-    for (uint32_t bounce = 0, next; bounce < depth_cap; bounce = next) {
+    for (uint32_t bounce = 0, next; bounce < cap; bounce = next) {
         next = bounce + (bounce == 0 && kFuseB1 ? 2u : 1u);
         const Queue in = queue(B, bounce & 1u), out = queue(B, next & 1u);
         const uint32_t* cin = B.counts + (size_t)bounce * G.nseg;
@@ -1381,15 +1347,6 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
     }
     return launches;
     }
-}
-
-template <int TR>
-uint32_t run_tr(bool count, bool march, QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Gen& R,
-                uint32_t depth_cap, uint32_t tail_at, uint32_t lds, uint32_t tail_grid) {
-    if (count && march) return run_batch<TR, true, true>(B, L, st, G, R, depth_cap, tail_at, lds, tail_grid);
-    if (count) return run_batch<TR, true, false>(B, L, st, G, R, depth_cap, tail_at, lds, tail_grid);
-    if (march) return run_batch<TR, false, true>(B, L, st, G, R, depth_cap, tail_at, lds, tail_grid);
-    return run_batch<TR, false, false>(B, L, st, G, R, depth_cap, tail_at, lds, tail_grid);
 }
 
 hipError_t ensure_events(Buffers& B, size_t n) {
@@ -1460,24 +1417,15 @@ void with_tr(int tr, F f) {
     }
 }
 
-template <int TR, bool MARCH, bool USER>
-void launch_query(const Query& Q, const OmParamsDev& P, uint32_t grid, uint32_t lds, hipStream_t st) {
-    if (Q.windows) {
-        if (Q.count)
-            hipLaunchKernelGGL((k_query_windows<TR, MARCH, USER, true>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.windows, Q.n, Q.hits, Q.counters);
-        else
-            hipLaunchKernelGGL((k_query_windows<TR, MARCH, USER, false>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.windows, Q.n, Q.hits, Q.counters);
-    } else if (Q.count)
-        hipLaunchKernelGGL((k_query<TR, MARCH, USER, true>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.n, Q.hits, Q.counters);
-    else
-        hipLaunchKernelGGL((k_query<TR, MARCH, USER, false>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.n, Q.hits, Q.counters);
-}
-template <int TR, bool MARCH>
-void launch_occluded(const Query& Q, const OmParamsDev& P, uint32_t grid, uint32_t lds, hipStream_t st) {
-    if (Q.count)
-        hipLaunchKernelGGL((k_occluded<TR, MARCH, true>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.windows, Q.n, Q.occluded, Q.counters);
-    else
-        hipLaunchKernelGGL((k_occluded<TR, MARCH, false>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.windows, Q.n, Q.occluded, Q.counters);
+// the current device's CU count and its LDS limit per workgroup
+struct DeviceLimits { int cus = 256, lds_max = 0; };
+DeviceLimits device_limits() {
+    DeviceLimits d;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipDeviceGetAttribute(&d.lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    return d;
 }
 
 }  // namespace
@@ -1540,15 +1488,14 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
         ns = concurrent ? std::min<uint32_t>(want, nb) : 1u;
         max_paths = (uint64_t)n_px * batch;
     }
-    const uint32_t depth_cap = L.P.max_depth > 1u ? L.P.max_depth : 1u;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const uint32_t cap = depth_cap(L.P);
+    const DeviceLimits dev = device_limits();
     const int tr = pick_trace(L.trace_mode, L.S);
     // segments, a multiple of the tail grouping: 4096 lanes per CU (8 workgroups of 512) for
     // traced worlds whose BVH2 sits in LDS, 8192 for marched worlds and L2-resident trees
-    const bool march = (L.S.n_msph + L.S.n_mbox + L.S.n_mtor + L.S.n_msdf) != 0u;
+    const bool march = has_marched(L.S);
+    // the marched set of C2's shape, no user objects (run_batch's EXACT)
+    const bool exact = march && L.S.n_msdf == 0u && MarchedC2Lds::matches(L.S.n_msph, L.S.n_mbox, L.S.n_mtor);
     // trees read through L2 (the wide BVH2 among them)
     const bool l2_tree = tr_base(tr) == TR_BVH2_GLOBAL || tr_base(tr) == TR_BVH4_GLOBAL || tr_base(tr) == TR_BVH2_WIDE;
     // the first bounce of the tail: the caller's (om_set_tail_bounce), or the default count of
@@ -1558,24 +1505,22 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
                            : (l2_tree ? kTailL2 : adaptive ? OM_WF_ADAPTIVE_TAIL
                               : max_paths > (1ull << 25) ? kTailBigBatch : kTailDefault) + (kFuseB1 ? 1u : 0u);
     const uint32_t lanes_per_cu = (march || l2_tree) ? OM_WF_LANES_PER_CU_WIDE : OM_WF_LANES_PER_CU;
-    const uint32_t nseg = deal_segments(max_paths, (uint32_t)cus, lanes_per_cu, kBlk, kTailSpb);
+    const uint32_t nseg = deal_segments(max_paths, (uint32_t)dev.cus, lanes_per_cu, kBlk, kTailSpb);
     // the fullest workgroup's share of the largest batch's deal (adaptive: max_paths bounds every
     // batch the device plans, and capacity() grows with the paths)
     const uint32_t segcap = batch_deal(max_paths, nseg).capacity();
     // (+ 1: the traced tail's claim counter, run_batch)
-    hipError_t e = grow(B, (uint64_t)nseg * segcap, count_rows(depth_cap) * nseg + 1u, (int)ns);
+    hipError_t e = grow(B, (uint64_t)nseg * segcap, count_rows(cap) * nseg + 1u, (int)ns);
     if (e != hipSuccess) { err = "wavefront buffer allocation failed"; return e; }
     const uint32_t lds = trace_lds(tr, L.S);
     // the traced tail: a resident grid, and the segment-count prefix in LDS behind the tree
-    const uint32_t tail_grid = (uint32_t)cus * kTailWgsPerCu;
-    int lds_max = 0;
-    (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-    if (!march && tail_at < depth_cap && tail_lds(lds, nseg) > (uint32_t)lds_max) {
+    const uint32_t tail_grid = (uint32_t)dev.cus * kTailWgsPerCu;
+    if (!march && tail_at < cap && tail_lds(lds, nseg) > (uint32_t)dev.lds_max) {
         err = "the tail's LDS request exceeds the device's limit";
         return hipErrorInvalidValue;
     }
     // every other launch of the variant requests `lds` (a wide tree at the 32-entry bound: 64 KiB of stack)
-    if (lds > (uint32_t)lds_max) {
+    if (lds > (uint32_t)dev.lds_max) {
         err = "the traversal's LDS request exceeds the device's limit";
         return hipErrorInvalidValue;
     }
@@ -1649,19 +1594,20 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
         R.batch = b;
         R.ad = ad;
         with_tr(tr, [&](auto t) {
-            launches += run_tr<decltype(t)::value>(L.count, march, QS, L, si, G, R, depth_cap, tail_at, lds, tail_grid);
+            constexpr int TR = decltype(t)::value;
+            with_flags({L.count, march, exact && exact_view_built<TR>()}, [&](auto count, auto mar, auto ex) {
+                if constexpr (mar || !ex) launches += run_batch<TR, count, mar, ex>(QS, L, si, G, R, tail_at, lds, tail_grid);
+            });
         });
         // accumulates in batch order: fixed spp needs it (Stats::add in sample order); an adaptive
         // stream's pixels are its own, so there it only keeps the streams in step and the progress
         // copies in order (unchained streams measured the same: 49.3 vs 49.2 ms per frame, r05_p6)
         if (ns > 1 && i > 0) (void)hipStreamWaitEvent(si, B.ev[kMaxSets + i - 1u], 0);
         const int ati = tm.mode == 1 ? tm.begin(si) : -1;
-        if (L.count)
-            hipLaunchKernelGGL(k_accumulate<true>, dim3(grid_a), dim3(kBlk), 0, si, L.P, L.stats, L.pixels, n_px,
+        with_flags({L.count}, [&](auto count) {
+            hipLaunchKernelGGL(k_accumulate<count>, dim3(grid_a), dim3(kBlk), 0, si, L.P, L.stats, L.pixels, n_px,
                                L.stats_by_pixel ? 1u : 0u, b, QS.res, QS.res_id, L.S.bloom, ad, L.counters);
-        else
-            hipLaunchKernelGGL(k_accumulate<false>, dim3(grid_a), dim3(kBlk), 0, si, L.P, L.stats, L.pixels, n_px,
-                               L.stats_by_pixel ? 1u : 0u, b, QS.res, QS.res_id, L.S.bloom, ad, L.counters);
+        });
         tm.end(ati, OM_KT_ACCUMULATE, si);
         // live progress: the cumulative credit after this batch, to the host word om_progress
         // hands out; ahead of the event the next batch's accumulate waits on, so the copies
@@ -1682,13 +1628,8 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
 
 // Workgroups the device holds at once at the bounce kernels' occupancy request (OM_WF_WAVES waves
 // per SIMD, 4 SIMDs per CU): the grid cap of the persistent k_query.
-uint32_t query_max_grid() {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return (uint32_t)cus * (uint32_t)(OM_WF_WAVES * 4 * 64 / kBlk);
-}
+uint32_t max_grid(const DeviceLimits& d) { return (uint32_t)d.cus * (uint32_t)(OM_WF_WAVES * 4 * 64 / kBlk); }
+uint32_t query_max_grid() { return max_grid(device_limits()); }
 
 void tree_regime(int trace_mode, const OmSceneDev& S, int32_t* regime, uint32_t* lds_bytes) {
     const int tr = pick_trace(trace_mode, S);
@@ -1706,25 +1647,31 @@ hipError_t query(const Query& Q, hipStream_t st) {
     if (Q.n == 0) return hipSuccess;
     const int tr = pick_trace(Q.trace_mode, Q.S);
     const uint32_t lds = trace_lds(tr, Q.S);
-    {   // refused here, not as a launch error (a wide tree at the 32-entry bound requests 64 KiB of stack)
-        int dev = 0, lds_max = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-        if (lds > (uint32_t)lds_max) return hipErrorInvalidValue;
-    }
-    const bool march = (Q.S.n_msph + Q.S.n_mbox + Q.S.n_mtor + Q.S.n_msdf) != 0u;
-    const bool user = Q.S.n_msdf != 0u;
+    // refused here, not as a launch error (a wide tree at the 32-entry bound requests 64 KiB of stack)
+    const DeviceLimits dev = device_limits();
+    if (lds > (uint32_t)dev.lds_max) return hipErrorInvalidValue;
+    const bool march = has_marched(Q.S);
+    const bool user = Q.S.n_msdf != 0u;                      // (a user object is a marched one)
     OmParamsDev P{};
     P.tmin = Q.tmin; P.tmax = Q.tmax; P.march_steps = Q.march_steps;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)Q.n + kBlk - 1u) / kBlk, query_max_grid());
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)Q.n + kBlk - 1u) / kBlk, max_grid(dev));
     with_tr(tr, [&](auto t) {
         constexpr int TR = decltype(t)::value;
-        if (Q.occluded) {
-            if (march) launch_occluded<TR, true>(Q, P, grid, lds, st);
-            else launch_occluded<TR, false>(Q, P, grid, lds, st);
-        } else if (user) launch_query<TR, true, true>(Q, P, grid, lds, st);
-        else if (march) launch_query<TR, true, false>(Q, P, grid, lds, st);
-        else launch_query<TR, false, false>(Q, P, grid, lds, st);
+        if (Q.occluded)
+            with_flags({march, Q.count}, [&](auto mar, auto count) {
+                hipLaunchKernelGGL((k_occluded<TR, mar, count>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.windows, Q.n,
+                                   Q.occluded, Q.counters);
+            });
+        else
+            with_flags({march, user, Q.windows != nullptr, Q.count}, [&](auto mar, auto usr, auto win, auto count) {
+                if constexpr (!mar && usr) return;
+                else if constexpr (win)
+                    hipLaunchKernelGGL((k_query_windows<TR, mar, usr, count>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays,
+                                       Q.windows, Q.n, Q.hits, Q.counters);
+                else
+                    hipLaunchKernelGGL((k_query<TR, mar, usr, count>), dim3(grid), dim3(kBlk), lds, st, Q.S, P, Q.rays, Q.n, Q.hits,
+                                       Q.counters);
+            });
     });
     return hipGetLastError();
 }

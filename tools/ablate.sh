@@ -122,7 +122,7 @@ if [ "$1" = build ]; then
   for k in ${VARIANTS:-${!V[@]}}; do
     ( printf 'extern "C" const char* om_build_id(void) { return "ablate-%s"; }\n' "$k" > _abl/bid_$k.cpp && \
       /opt/rocm/bin/hipcc ${V[$k]} -shared -o _abl/lib_$k.so $SRC/om_world.cpp $SRC/om_bvh.cpp $SRC/om_image.cpp $SRC/om_tiles.cpp \
-        $SRC/om_shard.cpp _abl/bid_$k.cpp -x hip $SRC/om_render.hip $SRC/om_wavefront.hip $SRC/om_display.hip $SRC/om_multi.hip \
+        $SRC/om_shard.cpp _abl/bid_$k.cpp -x hip $SRC/om_render.hip $SRC/om_megakernel.hip $SRC/om_wavefront.hip $SRC/om_display.hip $SRC/om_multi.hip \
         -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib > _abl/$k.log 2>&1 && echo "built $k" ) &
   done
   wait
