@@ -106,7 +106,7 @@ struct Builder {
 
     // builds items[begin,end) ; returns node index
     // SAH down to depth kSahDepth, then median splits: depth <= kSahDepth + log2(n)
-    // keeps every tree within the traversal stacks (24 entries, 64 for the global BVH).
+    // keeps every tree within the traversal stacks (kB2Stack entries, 64 for the global BVH).
     static constexpr uint32_t kSahDepth = 10;
     uint32_t build(uint32_t begin, uint32_t end, uint32_t depth = 0) {
         Box bb; bb.empty(); Box cb; cb.empty();
@@ -252,82 +252,26 @@ bool thin_sphere(const Mat4& l2w) {
     return 8.0 * u * D * D * rmax / (rmin * rmin) > margin;
 }
 
-void build_bvh(const om_world& w, FrozenWorld& fw) {
-    Builder b;
-    std::vector<uint32_t> always;
-    const double kHuge = 100.0;  // a bound larger than this is tested outside the BVH
-    auto add = [&](const Box& box, uint32_t gi, bool thin = false) {
-        double ext = 0.0;
-        for (int i = 0; i < 3; ++i) ext = std::max(ext, box.hi[i] - box.lo[i]);
-        if (ext > 2.0 * kHuge || thin) { always.push_back(gi); return; }
-        Item it; it.b = box; it.gi = gi;
-        for (int i = 0; i < 3; ++i) it.c[i] = 0.5 * (box.lo[i] + box.hi[i]);
-        b.items.push_back(it);
-    };
-    for (size_t i = 0; i < w.spheres.size(); ++i) add(affine_box(w.spheres[i].l2w, -1.0), fw.offsets[K_SPHERE] + (uint32_t)i, thin_sphere(w.spheres[i].l2w));
-    for (size_t i = 0; i < w.cubes.size(); ++i) add(affine_box(w.cubes[i].l2w, 0.5), fw.offsets[K_CUBE] + (uint32_t)i);
-    for (size_t i = 0; i < w.triangles.size(); ++i) add(bary_box(w.triangles[i], false), fw.offsets[K_TRI] + (uint32_t)i);
-    for (size_t i = 0; i < w.planes.size(); ++i) always.push_back(fw.offsets[K_PLANE] + (uint32_t)i);
-    for (size_t i = 0; i < w.parallelograms.size(); ++i) add(bary_box(w.parallelograms[i], true), fw.offsets[K_PARA] + (uint32_t)i);
-    std::sort(always.begin(), always.end());
-    fw.always = always;
-    if (!b.items.empty()) b.build(0, (uint32_t)b.items.size());
-    fw.bvh = b.nodes;
-    fw.bvh_prims = b.order;
-    build_skip_bvh(w, fw);
-}
+// The builder in stages, each with one output; build_bvh at the end of the file runs them in order on
+// the fresh FrozenWorld that freeze hands it.
+namespace {
 
-// Stackless layout: the SAH tree over the affine primitives (spheres,
-// cubes) and, from OM_BARY_TREE_MIN of them on, the triangles and parallelograms (§5.17),
-// re-emitted in depth-first order with a skip ("miss") link per node, and the
-// primitives' test records copied in leaf order so a leaf owns a contiguous run.
-// Everything else (planes, huge bounds, barycentric primitives below the threshold or with a
-// non-finite value) goes to always2.
-void build_bvh4(FrozenWorld& fw);
+// Stage 1, select: every traced primitive once, as an item of the SAH builder or as a record tested
+// outside the trees (`always`, ascending gi: the kinds are visited in gi order) with its conservative
+// box, infinite when unbounded.  Outside go the planes, a bound above kHuge and a thin sphere (all
+// unbounded: a huge sphere's inflation would cover the scene).  leaf_trees = false selects for the
+// global BVH, which takes every triangle and parallelogram.  leaf_trees = true selects for the
+// leaf-record trees (SBVH / BVH2 / BVH4): from OM_BARY_TREE_MIN of them on (§5.17), the
+// triangles and parallelograms with a finite frozen record and a finite box are items beside the
+// spheres and cubes (a huge one outside with its box); one with a non-finite value is outside and
+// unbounded, so no cull ever sees a NaN.  Below the threshold every one of them is outside with its
+// bary_box, the layout of every world before meshes.
+struct Selection { std::vector<Item> items; std::vector<OmAlwaysRec> always; };
 
-void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
-    Builder b;
-    std::vector<uint32_t> always;
-    const double kHuge = 100.0;
-    auto add = [&](const Box& box, uint32_t gi, bool thin = false) {
-        double ext = 0.0;
-        for (int i = 0; i < 3; ++i) ext = std::max(ext, box.hi[i] - box.lo[i]);
-        if (ext > 2.0 * kHuge || thin) { always.push_back(gi); return; }
-        Item it; it.b = box; it.gi = gi;
-        for (int i = 0; i < 3; ++i) it.c[i] = 0.5 * (box.lo[i] + box.hi[i]);
-        b.items.push_back(it);
-    };
-    for (size_t i = 0; i < w.spheres.size(); ++i) add(affine_box(w.spheres[i].l2w, -1.0), fw.offsets[K_SPHERE] + (uint32_t)i, thin_sphere(w.spheres[i].l2w));
-    for (size_t i = 0; i < w.cubes.size(); ++i) add(affine_box(w.cubes[i].l2w, 0.5), fw.offsets[K_CUBE] + (uint32_t)i);
-    // Triangles and parallelograms: from OM_BARY_TREE_MIN of them on, the ones with
-    // a finite frozen record and a finite box go to the SAH builder beside the spheres and cubes
-    // (a huge one to always2 with its box, like a huge sphere); one with a non-finite value becomes
-    // an unbounded always2 record, so no cull ever sees a NaN.  Below the threshold every one of
-    // them is in always2 with its bary_box, the layout of every world before meshes.
-    auto bary_finite = [](const OmBary& r, const Box& bx) {
-        const float* f = (const float*)&r;
-        for (size_t k = 0; k < sizeof(OmBary) / 4u; ++k) if (!std::isfinite(f[k])) return false;
-        for (int i = 0; i < 3; ++i) if (!std::isfinite(bx.lo[i]) || !std::isfinite(bx.hi[i])) return false;
-        return true;
-    };
-    std::vector<uint8_t> tri_ok(w.triangles.size()), para_ok(w.parallelograms.size());
-    size_t n_bary_ok = 0;
-    for (size_t i = 0; i < w.triangles.size(); ++i) n_bary_ok += (tri_ok[i] = bary_finite(fw.tri[i], bary_box(w.triangles[i], false)));
-    for (size_t i = 0; i < w.parallelograms.size(); ++i) n_bary_ok += (para_ok[i] = bary_finite(fw.para[i], bary_box(w.parallelograms[i], true)));
-    const bool bary_tree = n_bary_ok >= (size_t)OM_BARY_TREE_MIN;
-    for (size_t i = 0; i < w.triangles.size(); ++i) {
-        if (bary_tree && tri_ok[i]) add(bary_box(w.triangles[i], false), fw.offsets[K_TRI] + (uint32_t)i);
-        else always.push_back(fw.offsets[K_TRI] + (uint32_t)i);
-    }
-    for (size_t i = 0; i < w.planes.size(); ++i) always.push_back(fw.offsets[K_PLANE] + (uint32_t)i);
-    for (size_t i = 0; i < w.parallelograms.size(); ++i) {
-        if (bary_tree && para_ok[i]) add(bary_box(w.parallelograms[i], true), fw.offsets[K_PARA] + (uint32_t)i);
-        else always.push_back(fw.offsets[K_PARA] + (uint32_t)i);
-    }
-    std::sort(always.begin(), always.end());
-    fw.always2 = always;
-    fw.always2_rec.clear();
-    for (uint32_t gi : always) {
+Selection select(const om_world& w, const FrozenWorld& fw, bool leaf_trees) {
+    Selection s;
+    const double kHuge = 100.0;  // a bound larger than this is tested outside the trees
+    auto outside = [&](uint32_t gi, const Box* box) {
         OmAlwaysRec r;
         r.gi = gi; r.pad = 0;
         if (gi < fw.offsets[K_SPHERE + 1]) {      // axis-aligned sphere: every off-diagonal entry of W2L is +-0
@@ -335,160 +279,192 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
             if (m[1] == 0.0f && m[2] == 0.0f && m[4] == 0.0f && m[6] == 0.0f && m[8] == 0.0f && m[9] == 0.0f)
                 r.pad = OM_ALWAYS_DIAG_SPHERE;
         }
-        Box bx;
-        bool bounded = true;
-        if (gi >= fw.offsets[K_TRI] && gi < fw.offsets[K_TRI + 1]) {
-            bx = bary_box(w.triangles[gi - fw.offsets[K_TRI]], false);
-            bounded = !bary_tree || tri_ok[gi - fw.offsets[K_TRI]];
-        } else if (gi >= fw.offsets[K_PARA] && gi < fw.offsets[K_PARA + 1]) {
-            bx = bary_box(w.parallelograms[gi - fw.offsets[K_PARA]], true);
-            bounded = !bary_tree || para_ok[gi - fw.offsets[K_PARA]];
-        } else bounded = false;   // planes; huge spheres/cubes (their inflation would cover the scene)
         for (int i = 0; i < 3; ++i) {
-            r.lo[i] = bounded ? std::nextafter((float)bx.lo[i], -INFINITY) : -INFINITY;
-            r.hi[i] = bounded ? std::nextafter((float)bx.hi[i], INFINITY) : INFINITY;
+            r.lo[i] = box ? std::nextafter((float)box->lo[i], -INFINITY) : -INFINITY;
+            r.hi[i] = box ? std::nextafter((float)box->hi[i], INFINITY) : INFINITY;
         }
-        fw.always2_rec.push_back(r);
-    }
-    fw.snodes.clear();
-    fw.srecs.clear();
-    fw.n_srec_bary = 0;
-    if (b.items.empty()) return;
-    uint32_t root = b.build(0, (uint32_t)b.items.size());
-    // internal nodes, leaves, and internal nodes on the deepest root-to-leaf path (the compressed
-    // tree's lane-stack bound, fw.b2_depth below) of the built tree
-    auto tree_stats = [&](uint32_t r, size_t& internal, size_t& leaves, uint32_t& tdepth) {
-        internal = 0; leaves = 0; tdepth = 0;
-        std::vector<std::pair<uint32_t, uint32_t>> st{{r, 1u}};
-        while (!st.empty()) {
-            const auto [n, d] = st.back();
-            st.pop_back();
-            const OmBvhNode& nd = b.nodes[n];
-            if (nd.left < 0) { ++leaves; continue; }
-            ++internal; tdepth = std::max(tdepth, d);
-            st.push_back({(uint32_t)nd.left, d + 1u}); st.push_back({(uint32_t)nd.right, d + 1u});
+        s.always.push_back(r);
+    };
+    auto add = [&](const Box& box, uint32_t gi, bool thin, bool boxed_outside) {
+        double ext = 0.0;
+        for (int i = 0; i < 3; ++i) ext = std::max(ext, box.hi[i] - box.lo[i]);
+        if (ext > 2.0 * kHuge || thin) { outside(gi, boxed_outside ? &box : nullptr); return; }
+        Item it; it.b = box; it.gi = gi;
+        for (int i = 0; i < 3; ++i) it.c[i] = 0.5 * (box.lo[i] + box.hi[i]);
+        s.items.push_back(it);
+    };
+    size_t n_bary_ok = 0;
+    struct Bary { std::vector<Box> box; std::vector<uint8_t> ok; };
+    auto measure = [&](const std::vector<BaryPrim>& prims, const std::vector<OmBary>& recs, bool para) {
+        Bary b;
+        for (size_t i = 0; i < prims.size(); ++i) {
+            const Box bx = bary_box(prims[i], para);
+            const float* f = (const float*)&recs[i];
+            bool ok = true;
+            for (size_t k = 0; k < sizeof(OmBary) / 4u; ++k) ok = ok && std::isfinite(f[k]);
+            for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(bx.lo[k]) && std::isfinite(bx.hi[k]);
+            b.box.push_back(bx); b.ok.push_back(ok);
+            n_bary_ok += ok;
+        }
+        return b;
+    };
+    const Bary tri = measure(w.triangles, fw.tri, false), para = measure(w.parallelograms, fw.para, true);
+    const bool bary_tree = n_bary_ok >= (size_t)OM_BARY_TREE_MIN;
+    auto add_bary = [&](const Bary& b, uint32_t gi0) {
+        for (size_t i = 0; i < b.box.size(); ++i) {
+            if (!leaf_trees || (bary_tree && b.ok[i])) add(b.box[i], gi0 + (uint32_t)i, false, true);
+            else outside(gi0 + (uint32_t)i, bary_tree ? nullptr : &b.box[i]);
         }
     };
-    size_t internal, leaves;
-    uint32_t tdepth;
-    tree_stats(root, internal, leaves, tdepth);
-    if (internal * sizeof(OmBvh2Node) + leaves * 4u > kB2LdsBudget) {    // read through L2: smaller leaves
-        std::vector<OmBvhNode> nodes8;
-        std::vector<uint32_t> order8;
-        nodes8.swap(b.nodes); order8.swap(b.order);
-        const uint32_t root8 = root;
-        b.max_leaf = OM_BVH_MAX_LEAF_L2; b.leaf_force = OM_BVH_LEAF_FORCE_L2;
-        root = b.build(0, (uint32_t)b.items.size());
-        tree_stats(root, internal, leaves, tdepth);
-        // the compressed BVH2 needs 15-bit node and leaf codes and a lane stack of <= 24 entries
-        // (om_upload_world's b2_ok): one record per leaf gives one leaf per bounded primitive, which
-        // breaks those limits from ~32k primitives on -- keep the max-leaf tree then
-        if (!(internal < 32768u && leaves < 32768u && tdepth <= 24u)) {
-            b.nodes.swap(nodes8); b.order.swap(order8);
-            root = root8;
-        }
+    for (size_t i = 0; i < w.spheres.size(); ++i) add(affine_box(w.spheres[i].l2w, -1.0), fw.offsets[K_SPHERE] + (uint32_t)i, thin_sphere(w.spheres[i].l2w), false);
+    for (size_t i = 0; i < w.cubes.size(); ++i) add(affine_box(w.cubes[i].l2w, 0.5), fw.offsets[K_CUBE] + (uint32_t)i, false, false);
+    add_bary(tri, fw.offsets[K_TRI]);
+    for (size_t i = 0; i < w.planes.size(); ++i) outside(fw.offsets[K_PLANE] + (uint32_t)i, nullptr);
+    add_bary(para, fw.offsets[K_PARA]);
+    return s;
+}
+
+// Stage 2, build: the SAH tree over the items (the root is node 0) with its stats, from the builder's
+// own nodes: internal nodes, leaves, internal nodes on the deepest root-to-leaf path (the compressed
+// tree's lane-stack bound) and the records of the largest leaf.
+struct Tree {
+    std::vector<OmBvhNode> nodes;
+    std::vector<uint32_t> order;
+    size_t internal = 0, leaves = 0;
+    uint32_t depth = 0, max_leaf = 0;
+};
+
+Tree sah_tree(Builder& b, uint32_t max_leaf, uint32_t leaf_force) {
+    Tree t;
+    b.max_leaf = max_leaf; b.leaf_force = leaf_force;
+    b.build(0, (uint32_t)b.items.size());
+    t.nodes.swap(b.nodes); t.order.swap(b.order);
+    std::vector<uint32_t> d(t.nodes.size(), 1u);             // parents precede children
+    for (size_t n = 0; n < t.nodes.size(); ++n) {
+        const OmBvhNode& nd = t.nodes[n];
+        if (nd.left < 0) { ++t.leaves; t.max_leaf = std::max(t.max_leaf, (uint32_t)nd.right); continue; }
+        ++t.internal; t.depth = std::max(t.depth, d[n]);
+        d[(uint32_t)nd.left] = d[(uint32_t)nd.right] = d[n] + 1u;
     }
-    // depth-first re-emission with skip links
-    std::vector<uint32_t> leaf_first(b.nodes.size(), 0);
+    return t;
+}
+
+// The tree of the leaf records.  One whose BVH2 is read through L2 (past kB2LdsBudget) is rebuilt with
+// the _L2 leaf sizes.  One record per leaf gives one leaf per bounded primitive, which breaks the
+// 16-bit codes and the lane stack (om::plan_trees' b2_ok) from ~32k primitives on: the max-leaf tree
+// is kept then.
+Tree build_tree(std::vector<Item> items) {
+    Builder b;
+    b.items = std::move(items);
+    Tree t = sah_tree(b, OM_BVH_MAX_LEAF, OM_BVH_LEAF_FORCE);
+    if (t.internal * sizeof(OmBvh2Node) + t.leaves * 4u > kB2LdsBudget) {
+        Tree l2 = sah_tree(b, OM_BVH_MAX_LEAF_L2, OM_BVH_LEAF_FORCE_L2);
+        if (l2.internal < kCode16Limit && l2.leaves < kCode16Limit && l2.depth <= kB2Stack) return l2;
+    }
+    return t;
+}
+
+// The global BVH over every bounded traced primitive: bvh, bvh_prims, always.
+void build_global(const om_world& w, FrozenWorld& fw) {
+    Builder b;
+    Selection s = select(w, fw, false);
+    for (const OmAlwaysRec& r : s.always) fw.always.push_back(r.gi);
+    b.items.swap(s.items);
+    if (b.items.empty()) return;
+    Tree t = sah_tree(b, OM_BVH_MAX_LEAF, OM_BVH_LEAF_FORCE);
+    fw.bvh.swap(t.nodes);
+    fw.bvh_prims.swap(t.order);
+}
+
+// Stage 3, the stackless layout: the tree re-emitted in depth-first order with a skip
+// ("miss") link per node (snodes), and the primitives' test records copied in leaf order so a leaf
+// owns a contiguous run (srecs, n_srec_bary).  -> per builder node, the first record of a leaf
+std::vector<uint32_t> emit_skip(const Tree& t, FrozenWorld& fw) {
+    std::vector<uint32_t> leaf_first(t.nodes.size(), 0);
     struct Emit {
-        const Builder& b; const FrozenWorld& fw; std::vector<OmSkipNode>& out; std::vector<OmAffineTest>& recs;
-        std::vector<uint32_t>& leaf_first; uint32_t& n_bary;
+        const Tree& t; FrozenWorld& fw; std::vector<uint32_t>& leaf_first;
         void rec(uint32_t n) {
-            const OmBvhNode& src = b.nodes[n];
-            const uint32_t idx = (uint32_t)out.size();
+            const OmBvhNode& src = t.nodes[n];
+            const uint32_t idx = (uint32_t)fw.snodes.size();
             OmSkipNode o;
             for (int i = 0; i < 3; ++i) { o.lo[i] = src.lo[i]; o.hi[i] = src.hi[i]; }
             o.skip = 0; o.leaf = 0xFFFFFFFFu;
-            out.push_back(o);
+            fw.snodes.push_back(o);
             if (src.left < 0) {
                 const uint32_t first = (uint32_t)(-src.left - 1), cnt = (uint32_t)src.right;
-                out[idx].leaf = ((uint32_t)recs.size() << 8) | cnt;
-                leaf_first[n] = (uint32_t)recs.size();
+                fw.snodes[idx].leaf = ((uint32_t)fw.srecs.size() << 8) | cnt;
+                leaf_first[n] = (uint32_t)fw.srecs.size();
                 for (uint32_t k = 0; k < cnt; ++k) {
-                    const uint32_t gi = b.order[first + k];
+                    const uint32_t gi = t.order[first + k];
                     const bool bary = gi >= fw.offsets[K_TRI];       // a slot with only its tag (om_layout.h)
                     const bool cube = !bary && gi >= fw.offsets[K_CUBE];
-                    OmAffineTest t = bary ? OmAffineTest{} : cube ? fw.cube_test[gi - fw.offsets[K_CUBE]] : fw.sph_test[gi];
+                    OmAffineTest r = bary ? OmAffineTest{} : cube ? fw.cube_test[gi - fw.offsets[K_CUBE]] : fw.sph_test[gi];
                     const uint32_t tag = gi | (cube ? OM_REC_CUBE : 0u) | (bary ? OM_REC_BARY : 0u);
-                    std::memcpy(&t.pad, &tag, 4);
-                    recs.push_back(t);
-                    n_bary += bary ? 1u : 0u;
+                    std::memcpy(&r.pad, &tag, 4);
+                    fw.srecs.push_back(r);
+                    fw.n_srec_bary += bary ? 1u : 0u;
                 }
             } else {
                 rec((uint32_t)src.left);
                 rec((uint32_t)src.right);
             }
-            out[idx].skip = (uint32_t)out.size();
+            fw.snodes[idx].skip = (uint32_t)fw.snodes.size();
         }
-    } e{b, fw, fw.snodes, fw.srecs, leaf_first, fw.n_srec_bary};
-    e.rec(root);
+    } e{t, fw, leaf_first};
+    e.rec(0u);
+    return leaf_first;
+}
 
-    // compressed BVH2: both child boxes in the parent (one 64-B read per visit), emitted
-    // breadth-first so the top levels, which every ray visits, are the first nodes: a tree
-    // too big for LDS stages that prefix there (om_wavefront.hip, OM_WF_HYB_BYTES).
-    // direct leaf codes: when every record index fits 11 bits and every leaf holds
-    // at most 15 records (S-traced: 482 records, leaves <= 2; every regime: DESIGN.md §5.6), a leaf child's 16-bit code is
-    // OM_LEAF | first << 4 | count, so the traversal needs no leaf-table read to enter a leaf;
-    // the table is still emitted (same order) for the other consumers.
-    // (both conditions checked here, not assumed from the builder's leaf cap: a count above 15
-    // would spill into the `first` bits)
-    int32_t max_leaf = 0;
-    for (const OmBvhNode& n : b.nodes)
-        if (n.left < 0) max_leaf = std::max(max_leaf, n.right);
-    const bool direct = fw.srecs.size() < 2048u && max_leaf <= 15;
-    struct Emit2 {
-        const Builder& b; const std::vector<uint32_t>& leaf_first; std::vector<OmBvh2Node>& out;
-        std::vector<uint32_t>& leaves;
-        bool direct;
-        std::vector<std::pair<uint32_t, uint32_t>> q;   // (builder node, output index)
-        uint32_t code(uint32_t c) {
-            const OmBvhNode& n = b.nodes[c];
-            if (n.left < 0) {
-                leaves.push_back((leaf_first[c] << 8) | (uint32_t)n.right);
-                if (direct) return OM_LEAF | (leaf_first[c] << 4) | (uint32_t)n.right;
-                return OM_LEAF | (uint32_t)(leaves.size() - 1);
-            }
-            out.push_back(OmBvh2Node{});
-            q.emplace_back(c, (uint32_t)(out.size() - 1));
-            return (uint32_t)(out.size() - 1);
-        }
-        void rec(uint32_t root) {
-            out.push_back(OmBvh2Node{});
-            q.emplace_back(root, 0u);
-            for (size_t h = 0; h < q.size(); ++h) {
-                const uint32_t n = q[h].first, idx = q[h].second;
-                const OmBvhNode& src = b.nodes[n];
-                const OmBvhNode& L = b.nodes[(uint32_t)src.left];
-                const OmBvhNode& R = b.nodes[(uint32_t)src.right];
-                OmBvh2Node o{};
-                for (int i = 0; i < 3; ++i) {
-                    OM_B2_LO(o, 0, i) = L.lo[i]; OM_B2_HI(o, 0, i) = L.hi[i];
-                    OM_B2_LO(o, 1, i) = R.lo[i]; OM_B2_HI(o, 1, i) = R.hi[i];
-                }
-                o.c0 = code((uint32_t)src.left);
-                o.c1 = code((uint32_t)src.right);
-                out[idx] = o;
-            }
-        }
-    } e2{b, leaf_first, fw.b2nodes, fw.b2leaves, direct, {}};
-    fw.b2nodes.clear();
-    fw.b2leaves.clear();
-    if (b.nodes[root].left < 0) {            // a single leaf: one node, second child an empty leaf
-        OmBvh2Node o{};
-        for (int i = 0; i < 3; ++i) {
-            OM_B2_LO(o, 0, i) = b.nodes[root].lo[i]; OM_B2_HI(o, 0, i) = b.nodes[root].hi[i];
-            OM_B2_LO(o, 1, i) = INFINITY; OM_B2_HI(o, 1, i) = -INFINITY;
-        }
-        fw.b2leaves.push_back((leaf_first[root] << 8) | (uint32_t)b.nodes[root].right);
-        fw.b2leaves.push_back(0u);
-        o.c0 = direct ? (OM_LEAF | (leaf_first[root] << 4) | (uint32_t)b.nodes[root].right) : (OM_LEAF | 0u);
-        o.c1 = direct ? OM_LEAF : (OM_LEAF | 1u);          // empty leaf: no records
-        fw.b2nodes.push_back(o);
-    } else {
-        e2.rec(root);
+// Stage 4, the compressed BVH2: both child boxes in the parent (one read per visit), emitted
+// breadth-first so the top levels, which every ray visits, are the first nodes: a tree too big for LDS
+// stages that prefix there (om_wavefront.hip, OM_WF_HYB_BYTES).  One walk for both forms: `box` stores
+// child k's box in a node, `leaf` makes the code of a leaf child from its (first record, count).  A
+// single leaf becomes one node whose second child is an empty leaf.
+template <class Node, class BoxFn, class LeafFn>
+void emit_bvh2(const Tree& t, const std::vector<uint32_t>& leaf_first, std::vector<Node>& out, BoxFn box, LeafFn leaf) {
+    OmBvhNode none{};
+    for (int i = 0; i < 3; ++i) { none.lo[i] = INFINITY; none.hi[i] = -INFINITY; }
+    const bool one = t.nodes[0].left < 0;
+    std::vector<std::pair<uint32_t, uint32_t>> q{{0u, 0u}};   // (builder node, output index)
+    out.assign(1, Node{});
+    auto code = [&](uint32_t c) {
+        if (t.nodes[c].left < 0) return leaf(leaf_first[c], (uint32_t)t.nodes[c].right);
+        out.push_back(Node{});
+        q.emplace_back(c, (uint32_t)(out.size() - 1));
+        return (uint32_t)(out.size() - 1);
+    };
+    for (size_t h = 0; h < q.size(); ++h) {
+        const OmBvhNode& src = t.nodes[q[h].first];
+        Node o{};
+        box(o, 0, one ? src : t.nodes[(uint32_t)src.left]);
+        box(o, 1, one ? none : t.nodes[(uint32_t)src.right]);
+        o.c0 = code(one ? 0u : (uint32_t)src.left);
+        o.c1 = one ? leaf(0u, 0u) : code((uint32_t)src.right);
+        out[q[h].second] = o;
     }
+}
+
+// The f32 form with 16-bit codes and its leaf table (b2nodes, b2leaves, b2_direct).  Direct leaf codes:
+// when every record index fits kDirectFirst16 and every leaf holds at most kLeafCountMax records
+// (S-traced: 482 records, leaves <= 2; every regime: DESIGN.md §5.6), a leaf child's code is
+// OM_LEAF | first << 4 | count, so the traversal needs no leaf-table read to enter a leaf; the table
+// is still emitted (same order) for the other consumers.  (Both conditions checked here, not assumed
+// from the builder's leaf cap: a larger count would spill into the `first` bits)
+void emit_b2(const Tree& t, const std::vector<uint32_t>& leaf_first, FrozenWorld& fw) {
+    const bool direct = fw.srecs.size() < kDirectFirst16 && t.max_leaf <= kLeafCountMax;
     fw.b2_direct = direct ? 1u : 0u;
-    fw.b2h.clear();
+    emit_bvh2(t, leaf_first, fw.b2nodes,
+              [](OmBvh2Node& o, int k, const OmBvhNode& c) {
+                  for (int i = 0; i < 3; ++i) { (k ? o.lo1 : o.lo0)[i] = c.lo[i]; (k ? o.hi1 : o.hi0)[i] = c.hi[i]; }
+              },
+              [&](uint32_t first, uint32_t cnt) {
+                  fw.b2leaves.push_back((first << 8) | cnt);
+                  return OM_LEAF | (direct ? (first << kLeafCountBits) | cnt : (uint32_t)(fw.b2leaves.size() - 1));
+              });
+}
+
+// The half-precision copy of b2nodes (b2h).
+void emit_b2h(FrozenWorld& fw) {
     for (const OmBvh2Node& n : fw.b2nodes) {
         OmBvh2NodeH h{};
         for (int i = 0; i < 3; ++i) {
@@ -498,63 +474,22 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
         h.c0 = (uint16_t)n.c0; h.c1 = (uint16_t)n.c1; h.pad = 0u;
         fw.b2h.push_back(h);
     }
-    // depth of the compressed tree (the traversal's stack bound)
-    std::vector<uint32_t> depth(fw.b2nodes.size(), 1);
-    fw.b2_depth = 1;
-    for (uint32_t i = 0; i < fw.b2nodes.size(); ++i) {   // parents precede children (BFS)
-        for (uint32_t c : {fw.b2nodes[i].c0, fw.b2nodes[i].c1})
-            if (!(c & OM_LEAF)) { depth[c] = depth[i] + 1; fw.b2_depth = std::max(fw.b2_depth, depth[c]); }
-    }
-    // wide form (OmBvh2NodeW): the same tree in the same breadth-first order with
-    // 32-bit child codes and direct leaf codes, emitted straight from the builder's nodes (the 16-bit
-    // codes above collide from index 32 768 on, so nothing here reads b2nodes / b2h / b2leaves).
-    // For every world whose records fit the leaf code; om::plan_trees checks the depth.
-    fw.b2w.clear();
-    fw.b2w_depth = 0;
-    fw.b2_max_leaf = (uint32_t)max_leaf;
-    if (fw.srecs.size() < (1u << 27) && max_leaf <= 15) {
-        auto planes = [](OmBvh2NodeW& o, int k, const OmBvhNode& c) {
-            for (int i = 0; i < 3; ++i) {
-                o.b[6 * k + i] = half_out(c.lo[i], false);
-                o.b[6 * k + 3 + i] = half_out(c.hi[i], true);
-            }
-        };
-        auto leaf_code = [&](uint32_t c) { return OM_LEAFW | (leaf_first[c] << 4) | (uint32_t)b.nodes[c].right; };
-        if (b.nodes[root].left < 0) {        // a single leaf: one node, second child an empty leaf
-            OmBvh2NodeW o{};
-            OmBvhNode none{};
-            for (int i = 0; i < 3; ++i) { none.lo[i] = INFINITY; none.hi[i] = -INFINITY; }
-            planes(o, 0, b.nodes[root]);
-            planes(o, 1, none);
-            o.c0 = leaf_code(root);
-            o.c1 = OM_LEAFW;
-            fw.b2w.push_back(o);
-            fw.b2w_depth = 1;
-        } else {
-            struct QE { uint32_t node, idx, depth; };
-            std::vector<QE> q{{root, 0u, 1u}};
-            fw.b2w.push_back(OmBvh2NodeW{});
-            auto code = [&](uint32_t c, uint32_t d) {
-                if (b.nodes[c].left < 0) return leaf_code(c);
-                fw.b2w.push_back(OmBvh2NodeW{});
-                q.push_back({c, (uint32_t)(fw.b2w.size() - 1), d});
-                return (uint32_t)(fw.b2w.size() - 1);
-            };
-            for (size_t h = 0; h < q.size(); ++h) {
-                const QE e = q[h];
-                const OmBvhNode& src = b.nodes[e.node];
-                OmBvh2NodeW o{};
-                planes(o, 0, b.nodes[(uint32_t)src.left]);
-                planes(o, 1, b.nodes[(uint32_t)src.right]);
-                o.c0 = code((uint32_t)src.left, e.depth + 1u);
-                o.c1 = code((uint32_t)src.right, e.depth + 1u);
-                fw.b2w[e.idx] = o;
-                fw.b2w_depth = std::max(fw.b2w_depth, e.depth);
-            }
-        }
-    }
-    // conservative world box of every leaf record (the tree's own item boxes)
-    fw.srec_box.clear();
+}
+
+// The wide form (b2w; OmBvh2NodeW): the same tree in the same order with half planes
+// and direct 32-bit codes, for every world whose records fit the leaf code (the 16-bit codes collide
+// from index kCode16Limit on, so nothing here reads b2nodes / b2h / b2leaves).
+void emit_b2w(const Tree& t, const std::vector<uint32_t>& leaf_first, FrozenWorld& fw) {
+    if (!(fw.srecs.size() < kDirectFirst32 && t.max_leaf <= kLeafCountMax)) return;
+    emit_bvh2(t, leaf_first, fw.b2w,
+              [](OmBvh2NodeW& o, int k, const OmBvhNode& c) {
+                  for (int i = 0; i < 3; ++i) { o.b[6 * k + i] = half_out(c.lo[i], false); o.b[6 * k + 3 + i] = half_out(c.hi[i], true); }
+              },
+              [](uint32_t first, uint32_t cnt) { return OM_LEAFW | (first << kLeafCountBits) | cnt; });
+}
+
+// Stage 5: the conservative world box of every leaf record (srec_box; the tree's own item boxes).
+void emit_srec_box(const om_world& w, FrozenWorld& fw) {
     for (const OmAffineTest& t : fw.srecs) {
         uint32_t tag;
         std::memcpy(&tag, &t.pad, 4);
@@ -566,16 +501,14 @@ void build_skip_bvh(const om_world& w, FrozenWorld& fw) {
         for (int i = 0; i < 3; ++i) fw.srec_box.push_back(std::nextafter((float)bx.lo[i], -INFINITY));
         for (int i = 0; i < 3; ++i) fw.srec_box.push_back(std::nextafter((float)bx.hi[i], INFINITY));
     }
-    build_bvh4(fw);
 }
 
-// BVH4: each wide node takes its BVH2 node's two children and keeps
-// replacing the internal child of largest surface area by that child's two children, up
-// to four.  Child boxes are the BVH2's (already conservative), so culling stays exact.
+// Stage 6, the BVH4 (b4nodes, b4h, b4_depth): each wide node takes its BVH2 node's two
+// children and keeps replacing the internal child of largest surface area by that child's two children,
+// up to four.  Child boxes are the BVH2's (already conservative), so culling stays exact.  Collapsed
+// from the 16-bit codes of b2nodes: none for a tree past them.
 void build_bvh4(FrozenWorld& fw) {
-    fw.b4nodes.clear();
-    fw.b4_depth = 0;
-    if (fw.b2nodes.empty()) return;
+    if (fw.b2nodes.empty() || fw.b2nodes.size() >= kCode16Limit || fw.b2leaves.size() >= kCode16Limit) return;
     struct Ch { uint32_t code; float lo[3], hi[3]; };
     auto kids = [&](uint32_t n, Ch* out) {
         const OmBvh2Node& N = fw.b2nodes[n];
@@ -625,7 +558,6 @@ void build_bvh4(FrozenWorld& fw) {
     } r{fw, kids, area};
     r.go(0, 1);
     // breadth-first renumbering with half-precision planes (trees read through L2, §5.7)
-    fw.b4h.clear();
     std::vector<uint32_t> order{0u}, pos(fw.b4nodes.size(), 0u);
     for (size_t h = 0; h < order.size(); ++h)
         for (uint16_t c : fw.b4nodes[order[h]].child)
@@ -641,6 +573,27 @@ void build_bvh4(FrozenWorld& fw) {
         }
         fw.b4h.push_back(o);
     }
+}
+
+}  // namespace
+
+void build_bvh(const om_world& w, FrozenWorld& fw) {
+    build_global(w, fw);
+    Selection s = select(w, fw, true);
+    for (const OmAlwaysRec& r : s.always) fw.always2.push_back(r.gi);
+    fw.always2_rec.swap(s.always);
+    if (s.items.empty()) return;
+    const Tree t = build_tree(std::move(s.items));
+    const std::vector<uint32_t> leaf_first = emit_skip(t, fw);
+    emit_b2(t, leaf_first, fw);
+    emit_b2h(fw);
+    emit_b2w(t, leaf_first, fw);
+    // the traversals' stack bounds: a single leaf still takes one node
+    fw.b2_depth = std::max(t.depth, 1u);
+    fw.b2w_depth = fw.b2w.empty() ? 0u : fw.b2_depth;
+    fw.b2_max_leaf = t.max_leaf;
+    emit_srec_box(w, fw);
+    build_bvh4(fw);
 }
 
 }  // namespace om

@@ -18,5 +18,4 @@ bool thin_sphere(const Mat4& l2w);
 // infinite plane, so a NaN box culls nothing)
 float half_value(uint16_t h);
 uint16_t half_out(float x, bool up);
-void build_skip_bvh(const om_world& w, FrozenWorld& fw);
 }

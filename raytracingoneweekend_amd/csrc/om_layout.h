@@ -206,6 +206,16 @@ struct OM_ALIGN16 OmBvh2NodeW {
 // of a gfx950 CU's 160 KiB still leaves two workgroups per CU; the builder's depth bound (kSahDepth + log2 n)
 // reaches 32 only past 2^22 records
 constexpr uint32_t kB2WideStack = 32u;
+// The tree limits the code layouts above imply (the builder keeps to them, om::plan_trees admits by them):
+// 16-bit codes hold node and leaf-table indices below the leaf bit; a direct leaf code holds the count
+// in its low 4 bits and the first record in the bits between them and the leaf bit
+constexpr uint32_t kCode16Limit = OM_LEAF;                          // b2nodes, b2leaves, b4nodes: fewer than this
+constexpr uint32_t kLeafCountBits = 4u, kLeafCountMax = (1u << kLeafCountBits) - 1u;   // 15 records
+constexpr uint32_t kDirectFirst16 = OM_LEAF >> kLeafCountBits;     // 2^11: srecs below this take direct 16-bit codes
+constexpr uint32_t kDirectFirst32 = OM_LEAFW >> kLeafCountBits;    // 2^27: srecs below this take the wide form
+static_assert((((kDirectFirst16 - 1u) << kLeafCountBits) | kLeafCountMax) == (0xFFFFu & ~OM_LEAF), "a direct 16-bit code's fields fill the bits below OM_LEAF");
+// lane-stack bounds of the 16-bit regimes (u16 entries per lane): the BVH2's internal depth, the BVH4's 3 per level + 3
+constexpr uint32_t kB2Stack = 24u, kB4Stack = 48u;
 // f32 BVH2 nodes + leaf table of at most this many bytes (nodes counted at their 64 B in memory)
 // are staged whole in LDS per workgroup; a bigger tree is read through L2 (half nodes, an LDS
 // prefix) and built with smaller leaves.  The wavefront stages the nodes OM_B2_NODE_STRIDE (80) B
@@ -251,7 +261,7 @@ struct OmSceneDev {
     uint32_t n_b2nodes, n_b2leaves;
     uint32_t b2_lds_bytes;        // nodes*64 + leaves*4 when within kB2LdsBudget, else 0 (global nodes); the megakernel
                                   // stages exactly these bytes, the wavefront nodes*80 + leaves*4 (b2_stage_bytes)
-    uint32_t b2_stack;           // lane-stack entries the tree needs (its internal depth, <= 24)
+    uint32_t b2_stack;           // lane-stack entries the tree needs (its internal depth, <= kB2Stack)
     uint32_t b2_direct;           // leaf codes are OM_LEAF | first_record << 4 | count (om_bvh.cpp), not table indices
     // BVH4 collapsed from the BVH2 (same leaf table / records / always2)
     const OmBvh4Node* b4nodes;

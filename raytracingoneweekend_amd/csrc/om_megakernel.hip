@@ -18,7 +18,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kBlockLds = 512;                 // the SBVH variants' workgroup
-constexpr int kStack2 = 24;                    // BVH2 lane-stack bound (om_upload_world checks the depth)
+constexpr int kStack2 = (int)kB2Stack;         // BVH2 lane-stack bound (om::plan_trees checks the depth)
 template <int MODE> constexpr int block_of() { return MODE == TR_SBVH_LDS || MODE == TR_SBVH_GLOBAL ? kBlockLds : kBlock; }
 // the variants whose leaves may hold triangles / parallelograms: the only ones with BARY instantiations
 template <int MODE> constexpr bool bary_built() { return MODE == TR_SBVH_LDS || MODE == TR_SBVH_GLOBAL || MODE == TR_BVH2_LDS; }

@@ -299,7 +299,7 @@ __device__ __forceinline__ void test_rec(const OmSceneDev& S, const OmAffineTest
 // (first record << 8) | count of the leaf with child code `code`: straight from a direct code
 // (OM_LEAF | first << 4 | count, om_bvh.cpp), else from the leaf table.
 __device__ __forceinline__ uint32_t leaf_payload(const OmSceneDev& S, uint32_t code, const uint32_t* leaves) {
-    return S.b2_direct ? ((((code >> 4) & 0x7FFu) << 8) | (code & 15u)) : leaves[code & (OM_LEAF - 1u)];
+    return S.b2_direct ? ((((code >> kLeafCountBits) & (kDirectFirst16 - 1u)) << 8) | (code & kLeafCountMax)) : leaves[code & (OM_LEAF - 1u)];
 }
 
 // Leaf of the BVH2/BVH4: its records, tested in place.
@@ -319,7 +319,7 @@ __device__ __forceinline__ void test_leaf_code(const OmSceneDev& S, const OmAffi
                                                F3 o, F3 d, float tmin, float& closest, int& best, Wk& w) {
     if constexpr (B2Codes<Node>::LEAF == OM_LEAFW) {
         // first < 2^27 does not fit test_leaf's 24 bits: the record pointer moves instead
-        test_leaf(S, recs + ((code & ~OM_LEAFW) >> 4), code & 15u, o, d, tmin, closest, best, w);
+        test_leaf(S, recs + ((code & ~OM_LEAFW) >> kLeafCountBits), code & kLeafCountMax, o, d, tmin, closest, best, w);
     } else {
         test_leaf(S, recs, leaf_payload(S, code, leaves), o, d, tmin, closest, best, w);
     }

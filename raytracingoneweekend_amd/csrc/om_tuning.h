@@ -159,7 +159,7 @@
 #define OM_B2_NODE_STRIDE 80
 #endif
 // Triangles + parallelograms (counted together; only the bounded ones with finite records) from
-// which build_skip_bvh puts them into the SBVH / BVH2 / BVH4 leaves beside the spheres and cubes
+// which select (om_bvh.cpp) puts them into the SBVH / BVH2 / BVH4 leaves beside the spheres and cubes
 // (DESIGN.md §5.17); a world with fewer keeps them in always2 and its frozen layout byte for byte.
 // NOT a measured crossover: 16 is above every world the repository renders, tests or benchmarks
 // with barycentric primitives in always2 (random_scene, tie_scene and kitchen_sink hold 2 each), so

@@ -63,7 +63,7 @@ namespace {
 constexpr uint32_t kNoSample = 0xFFFFFFFFu;
 #define OM_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(OM_WF_WAVES, OM_WF_WAVES)))   // occupancy request (waves per SIMD)
 constexpr int kBlk = OM_WF_BLOCK;                                 // workgroup = one queue segment
-constexpr int kStackDepth = 24;                                   // BVH2 per-lane LDS stack bound (entries)
+constexpr int kStackDepth = (int)kB2Stack;                        // BVH2 per-lane LDS stack bound (entries)
 // f32 BVH2 nodes staged in LDS sit OM_B2_NODE_STRIDE bytes apart (om_tuning.h)
 constexpr uint32_t kB2Stride = OM_B2_NODE_STRIDE;
 static_assert(kB2Stride % 16u == 0u && kB2Stride >= sizeof(OmBvh2Node), "16-B aligned node slots");

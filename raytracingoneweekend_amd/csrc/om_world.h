@@ -56,7 +56,7 @@ struct FrozenWorld {
     std::vector<OmBvh2NodeW> b2w;      // the BVH2 with 32-bit child codes (every world with a BVH2 whose records fit them)
     uint32_t b2w_depth = 0;            // its depth (stack bound)
     uint32_t b2_max_leaf = 0;          // records in the largest leaf of the BVH2
-    std::vector<OmBvh4Node> b4nodes;   // 4-wide tree collapsed from b2nodes (leaf codes index b2leaves)
+    std::vector<OmBvh4Node> b4nodes;   // 4-wide tree collapsed from b2nodes (leaf codes index b2leaves; none past the 16-bit codes)
     std::vector<OmBvh4NodeH> b4h;      // the same tree breadth-first, half-precision boxes rounded outward
     uint32_t b4_depth = 0;             // its depth
     uint32_t counts[K_N];
@@ -67,7 +67,7 @@ struct FrozenWorld {
 // host-only tests/cpp/tree_regimes.cpp reports them).  A zero *_lds_bytes means "not staged":
 // the tree is read through L2 (BVH2 / BVH4) or from global memory (the megakernel's SBVH).
 struct TreePlan {
-    bool b2_ok = false;            // compressed BVH2 usable: 15-bit node / leaf codes, depth <= 24
+    bool b2_ok = false;            // compressed BVH2 usable: node / leaf counts < kCode16Limit, depth <= kB2Stack
     uint32_t n_b2nodes = 0, n_b2leaves = 0, b2_direct = 0;
     uint32_t b2_stack = 0;         // lane-stack entries: one push per internal level, deepest included
     uint32_t b2_lds_bytes = 0;     // nodes (64 B each) + leaf table, rounded to 16, when within kB2LdsBudget
@@ -76,7 +76,7 @@ struct TreePlan {
     uint32_t b4_lds_bytes = 0;     // nodes (112 B each) + leaf table, rounded to 16, when within kB4LdsBudget
     uint32_t lds_bytes = 0;        // SBVH nodes + records when within kLdsBudget (at least 16)
     // wide BVH2 (32-bit codes): usable when the records fit the direct leaf code
-    // (first < 2^27, count <= 15) and the depth the u32 lane stack's bound
+    // (first < kDirectFirst32, count <= kLeafCountMax) and the depth the u32 lane stack's bound
     bool b2w_ok = false;
     uint32_t n_b2wnodes = 0, b2w_stack = 0;
 };
@@ -101,21 +101,21 @@ inline TreePlan plan_trees(const FrozenWorld& fw) {
     p.lds_bytes = lds <= kLdsBudget ? (uint32_t)(lds < 16 ? 16 : lds) : 0u;
     // compressed BVH2: usable when node and leaf ids fit the 15-bit codes and its depth fits
     // the lane-stack bound (otherwise the wavefront path uses the global-memory BVH)
-    p.b2_ok = !fw.b2nodes.empty() && fw.b2nodes.size() < 32768u && fw.b2leaves.size() < 32768u &&
-              fw.b2_depth <= 24u;   // lane stack bound (om_wavefront.hip kStackDepth)
+    p.b2_ok = !fw.b2nodes.empty() && fw.b2nodes.size() < kCode16Limit && fw.b2leaves.size() < kCode16Limit &&
+              fw.b2_depth <= kB2Stack;
     p.n_b2nodes = p.b2_ok ? (uint32_t)fw.b2nodes.size() : 0u;
     p.n_b2leaves = p.b2_ok ? (uint32_t)fw.b2leaves.size() : 0u;
     p.b2_direct = p.b2_ok ? fw.b2_direct : 0u;
     p.b2_stack = p.b2_ok ? fw.b2_depth : 0u;
     const size_t b2_bytes = fw.b2nodes.size() * sizeof(OmBvh2Node) + fw.b2leaves.size() * 4u;
     p.b2_lds_bytes = (p.b2_ok && b2_bytes <= kB2LdsBudget) ? (uint32_t)((b2_bytes + 15u) & ~(size_t)15u) : 0u;
-    // BVH4 (same leaf table): within the 48-entry bound of om_wavefront.hip
+    // BVH4 (same leaf table): within its lane-stack bound
     const uint32_t b4_stack = 3u * fw.b4_depth + 3u;
-    p.b4_ok = p.b2_ok && !fw.b4nodes.empty() && fw.b4nodes.size() < 32768u && b4_stack <= 48u;
+    p.b4_ok = p.b2_ok && !fw.b4nodes.empty() && fw.b4nodes.size() < kCode16Limit && b4_stack <= kB4Stack;
     p.b4_stack = p.b4_ok ? b4_stack : 0u;
     const size_t b4_bytes = fw.b4nodes.size() * sizeof(OmBvh4Node) + fw.b2leaves.size() * 4u;
     p.b4_lds_bytes = (p.b4_ok && b4_bytes <= kB4LdsBudget) ? (uint32_t)((b4_bytes + 15u) & ~(size_t)15u) : 0u;
-    p.b2w_ok = !fw.b2w.empty() && fw.b2w.size() < OM_LEAFW && fw.srecs.size() < (1u << 27) && fw.b2_max_leaf <= 15u &&
+    p.b2w_ok = !fw.b2w.empty() && fw.b2w.size() < OM_LEAFW && fw.srecs.size() < kDirectFirst32 && fw.b2_max_leaf <= kLeafCountMax &&
                fw.b2w_depth <= kB2WideStack &&
                fw.offsets[K_N] <= OM_REC_GI;   // its kernels are the OM_REC_BARY forms: gi beside two kind bits
     p.n_b2wnodes = p.b2w_ok ? (uint32_t)fw.b2w.size() : 0u;
@@ -130,8 +130,7 @@ inline void fill_tree_info(const FrozenWorld& fw, const TreePlan& p, om_tree_inf
     out->always_tested = (uint32_t)fw.always2.size();
     out->b2_nodes = (uint32_t)fw.b2nodes.size();
     out->b2_leaves = (uint32_t)fw.b2leaves.size();
-    // (past the 15-bit codes b2_depth is computed from colliding codes: the wide emission's is the tree's)
-    out->b2_depth = fw.b2w.empty() ? fw.b2_depth : fw.b2w_depth;
+    out->b2_depth = fw.b2_depth;
     out->b2_max_leaf = fw.b2_max_leaf;
     if (p.b2_ok) {
         out->regime = p.b2_lds_bytes ? OM_TREE_LDS : OM_TREE_L2;

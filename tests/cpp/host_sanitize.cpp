@@ -156,7 +156,7 @@ int main() {
         om::FrozenWorld fw;
         w->freeze(fw);
         EXPECT(fw.offsets[8] >= 39000u);
-        EXPECT(!fw.b2nodes.empty() && fw.b2nodes.size() < 32768u && fw.b2leaves.size() < 32768u && fw.b2_depth <= 24u);
+        EXPECT(!fw.b2nodes.empty() && fw.b2nodes.size() < kCode16Limit && fw.b2leaves.size() < kCode16Limit && fw.b2_depth <= kB2Stack);
         std::printf("S-40k: %u prims, %zu BVH2 nodes, %zu leaves, depth %u\n", fw.offsets[8], fw.b2nodes.size(),
                     fw.b2leaves.size(), fw.b2_depth);
         om_world_destroy(w);

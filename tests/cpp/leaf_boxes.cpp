@@ -27,42 +27,12 @@
 #include "../../raytracingoneweekend_amd/csrc/om_tuning.h"
 #include "../../raytracingoneweekend_amd/csrc/om_world.h"
 #include "ottomarcher.h"
+#include "world_file.h"
 
 namespace {
 
 int g_fail = 0;
 #define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #c); ++g_fail; } } while (0)
-
-bool read_exact(std::FILE* f, void* p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
-
-bool load(const char* path, om_world* w) {
-    std::FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    const om_material m = om_material_lambertian(0.5f, 0.5f, 0.5f);
-    uint32_t n = 0;
-    bool ok = read_exact(f, &n, 4);
-    for (uint32_t k = 0; ok && k < n; ++k) {
-        uint32_t tag = 0;
-        ok = read_exact(f, &tag, 4);
-        if (!ok) break;
-        if (tag == 1u) {
-            float v[4];
-            ok = read_exact(f, v, sizeof v) && om_world_add_sphere_radius(w, v, v[3], &m) == OM_OK;
-        } else if (tag == 2u || tag == 3u) {
-            float l2w[16];
-            ok = read_exact(f, l2w, sizeof l2w) &&
-                 (tag == 2u ? om_world_add_sphere(w, l2w, &m) : om_world_add_cube(w, l2w, &m)) == OM_OK;
-        } else if (tag == 5u || tag == 6u) {
-            float p[9];
-            ok = read_exact(f, p, sizeof p) &&
-                 (tag == 5u ? om_world_add_triangle(w, p, p + 3, p + 6, &m) : om_world_add_parallelogram(w, p, p + 3, p + 6, &m)) == OM_OK;
-        } else {
-            ok = false;
-        }
-    }
-    std::fclose(f);
-    return ok;
-}
 
 struct Box { float v[6]; };
 typedef std::vector<Box> Chain;
@@ -122,7 +92,7 @@ void walk_sbvh(const Out& o, uint32_t n, Chain& c) {
 
 // (first, count) of a 16-bit leaf code (om_trace.h leaf_payload)
 void leaf16(const om::FrozenWorld& fw, uint32_t code, uint32_t& first, uint32_t& cnt) {
-    if (fw.b2_direct) { first = (code >> 4) & 0x7FFu; cnt = code & 15u; return; }
+    if (fw.b2_direct) { first = (code >> kLeafCountBits) & (kDirectFirst16 - 1u); cnt = code & kLeafCountMax; return; }
     const uint32_t l = fw.b2leaves[code & (OM_LEAF - 1u)];
     first = l >> 8; cnt = l & 255u;
 }
@@ -160,7 +130,7 @@ void walk_b2w(const Out& o, uint32_t n, Chain& c) {
         Box b;
         for (int i = 0; i < 3; ++i) { b.v[i] = om::half_value(N.b[6 * k + i]); b.v[3 + i] = om::half_value(N.b[6 * k + 3 + i]); }
         c.push_back(b);
-        if (code & OM_LEAFW) o.leaf((code & ~OM_LEAFW) >> 4, code & 15u, c);
+        if (code & OM_LEAFW) o.leaf((code & ~OM_LEAFW) >> kLeafCountBits, code & kLeafCountMax, c);
         else walk_b2w(o, code, c);
         c.pop_back();
     }

@@ -1,7 +1,7 @@
 // mesh_regimes.cpp — which traversal regime each mesh test world lands in, and where its triangles
 // are kept (host code only; the mesh counterpart of tree_regimes.cpp).
 //
-// From OM_BARY_TREE_MIN triangles + parallelograms on, build_skip_bvh (om_bvh.cpp) puts them into
+// From OM_BARY_TREE_MIN triangles + parallelograms on, select (om_bvh.cpp) puts them into
 // the SBVH / BVH2 / BVH4 leaves as OM_REC_BARY records beside the spheres and cubes; below it they
 // stay in always2.  tests/test_mesh_regimes.py builds the worlds of
 // tests/mesh_common.py in numpy, writes each to a file (mesh_common.dump: u32 item count, then per
@@ -32,46 +32,12 @@
 #include "../../raytracingoneweekend_amd/csrc/om_tuning.h"
 #include "../../raytracingoneweekend_amd/csrc/om_world.h"
 #include "ottomarcher.h"
+#include "world_file.h"
 
 namespace {
 
 int g_fail = 0;
 #define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #c); ++g_fail; } } while (0)
-
-bool read_exact(std::FILE* f, void* p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
-
-bool load(const char* path, om_world* w) {
-    std::FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    const om_material m = om_material_lambertian(0.5f, 0.5f, 0.5f);
-    uint32_t n = 0;
-    bool ok = read_exact(f, &n, 4);
-    for (uint32_t k = 0; ok && k < n; ++k) {
-        uint32_t tag = 0;
-        ok = read_exact(f, &tag, 4);
-        if (!ok) break;
-        if (tag == 1u) {
-            float v[4];
-            ok = read_exact(f, v, sizeof v) && om_world_add_sphere_radius(w, v, v[3], &m) == OM_OK;
-        } else if (tag == 2u || tag == 3u) {
-            float l2w[16];
-            ok = read_exact(f, l2w, sizeof l2w) &&
-                 (tag == 2u ? om_world_add_sphere(w, l2w, &m) : om_world_add_cube(w, l2w, &m)) == OM_OK;
-        } else if (tag == 4u) {
-            uint32_t nv = 0, nt = 0;
-            ok = read_exact(f, &nv, 4) && read_exact(f, &nt, 4) && nv <= (1u << 24) && nt <= (1u << 24);
-            if (!ok) break;
-            std::vector<float> v((size_t)nv * 3u);
-            std::vector<uint32_t> idx((size_t)nt * 3u);
-            ok = read_exact(f, v.data(), v.size() * 4u) && read_exact(f, idx.data(), idx.size() * 4u) &&
-                 om_world_add_triangles(w, v.data(), nv, idx.data(), nt, &m) == OM_OK;
-        } else {
-            ok = false;
-        }
-    }
-    std::fclose(f);
-    return ok;
-}
 
 void report(const char* name, const om_world* w) {
     om::FrozenWorld fw;

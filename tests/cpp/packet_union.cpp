@@ -57,8 +57,8 @@ double trace(const om::FrozenWorld& fw, V o, V d, double tmax, Trav* tv, V* nrm)
     double closest = tmax, t;
     V n{0, 1, 0};
     auto leaf = [&](uint32_t code) {
-        const uint32_t first = fw.b2_direct ? ((code >> 4) & 0x7FFu) : fw.b2leaves[code & 0x7FFFu] >> 8;
-        const uint32_t cnt = fw.b2_direct ? (code & 15u) : fw.b2leaves[code & 0x7FFFu] & 255u;
+        const uint32_t first = fw.b2_direct ? ((code >> kLeafCountBits) & (kDirectFirst16 - 1u)) : fw.b2leaves[code & (OM_LEAF - 1u)] >> 8;
+        const uint32_t cnt = fw.b2_direct ? (code & kLeafCountMax) : fw.b2leaves[code & (OM_LEAF - 1u)] & 255u;
         if (tv) { tv->leaf_visits++; tv->leaves.insert(code); }
         for (uint32_t k = 0; k < cnt; ++k) {
             uint32_t tag;

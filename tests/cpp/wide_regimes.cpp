@@ -24,52 +24,18 @@
 #include "../../raytracingoneweekend_amd/csrc/om_tuning.h"
 #include "../../raytracingoneweekend_amd/csrc/om_world.h"
 #include "ottomarcher.h"
+#include "world_file.h"
 
 namespace {
 
 int g_fail = 0;
 #define EXPECT(c) do { if (!(c)) { if (g_fail < 20) std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #c); ++g_fail; } } while (0)
 
-bool read_exact(std::FILE* f, void* p, size_t n) { return n == 0 || std::fread(p, 1, n, f) == n; }
-
-bool load(const char* path, om_world* w) {
-    std::FILE* f = std::fopen(path, "rb");
-    if (!f) return false;
-    const om_material m = om_material_lambertian(0.5f, 0.5f, 0.5f);
-    uint32_t n = 0;
-    bool ok = read_exact(f, &n, 4);
-    for (uint32_t k = 0; ok && k < n; ++k) {
-        uint32_t tag = 0;
-        ok = read_exact(f, &tag, 4);
-        if (!ok) break;
-        if (tag == 1u) {
-            float v[4];
-            ok = read_exact(f, v, sizeof v) && om_world_add_sphere_radius(w, v, v[3], &m) == OM_OK;
-        } else if (tag == 2u || tag == 3u) {
-            float l2w[16];
-            ok = read_exact(f, l2w, sizeof l2w) &&
-                 (tag == 2u ? om_world_add_sphere(w, l2w, &m) : om_world_add_cube(w, l2w, &m)) == OM_OK;
-        } else if (tag == 4u) {
-            uint32_t nv = 0, nt = 0;
-            ok = read_exact(f, &nv, 4) && read_exact(f, &nt, 4) && nv <= (1u << 24) && nt <= (1u << 24);
-            if (!ok) break;
-            std::vector<float> v((size_t)nv * 3u);
-            std::vector<uint32_t> idx((size_t)nt * 3u);
-            ok = read_exact(f, v.data(), v.size() * 4u) && read_exact(f, idx.data(), idx.size() * 4u) &&
-                 om_world_add_triangles(w, v.data(), nv, idx.data(), nt, &m) == OM_OK;
-        } else {
-            ok = false;
-        }
-    }
-    std::fclose(f);
-    return ok;
-}
-
 struct Range { uint32_t first, count; };
 bool wide_leaf(uint32_t c) { return c >= OM_LEAFW; }
-Range wide_range(uint32_t c) { return Range{(c & ~OM_LEAFW) >> 4, c & 15u}; }
+Range wide_range(uint32_t c) { return Range{(c & ~OM_LEAFW) >> kLeafCountBits, c & kLeafCountMax}; }
 Range narrow_range(const om::FrozenWorld& fw, uint32_t c) {
-    if (fw.b2_direct) return Range{(c >> 4) & 0x7FFu, c & 15u};
+    if (fw.b2_direct) return Range{(c >> kLeafCountBits) & (kDirectFirst16 - 1u), c & kLeafCountMax};
     const uint32_t l = fw.b2leaves[c & (OM_LEAF - 1u)];
     return Range{l >> 8, l & 255u};
 }
@@ -162,7 +128,7 @@ void report(const char* name, const om_world* w) {
         EXPECT(once == fw.srecs.size());
         EXPECT(wk.nodes == fw.b2w.size());
         EXPECT(wk.depth == fw.b2w_depth);
-        EXPECT(wk.max_leaf == fw.b2_max_leaf && wk.max_leaf <= 15u);
+        EXPECT(wk.max_leaf == fw.b2_max_leaf && wk.max_leaf <= kLeafCountMax);
         EXPECT(wk.bad_planes == 0u && wk.bad_boxes == 0u);
     }
     om_tree_info ti{};

@@ -1,7 +1,7 @@
 """Where the triangles of the mesh test worlds are kept, and which tree regime each world lands in
 (CPU only; the mesh counterpart of test_tree_regimes.py).
 
-From OM_BARY_TREE_MIN triangles + parallelograms on, build_skip_bvh puts them into the SBVH / BVH2 /
+From OM_BARY_TREE_MIN triangles + parallelograms on, the builder (om_bvh.cpp select) puts them into the SBVH / BVH2 /
 BVH4 leaves beside the spheres and cubes.  tests/test_gpu_mesh.py traces and
 renders the worlds of tests/mesh_common.py against the oracle; this test pins, from the host-only
 report of tests/cpp/mesh_regimes.cpp on the same numpy arrays, that each of them IS in the regime it
