@@ -2,6 +2,7 @@
 // the winner, the camera ray and the counter flush; shared by the megakernel
 // (om_megakernel.hip) and the wavefront pipeline (om_wavefront.hip).
 #pragma once
+#include "om_b2_planes.h"
 #include "om_device.h"
 #include "om_layout.h"
 #include "om_tuning.h"
@@ -19,8 +20,10 @@ template <int K> __device__ __forceinline__ float b2p(const OmBvh2NodeH& N) { re
 template <int K> __device__ __forceinline__ float b2p(const OmBvh2NodeW& N) { return h2f(N.b[K]); }
 // Child codes of a BVH2 node type: the leaf bit and the lane-stack entry that holds a code
 // (16-bit codes, OM_LEAF; OmBvh2NodeW: 32-bit codes, OM_LEAFW).
-template <class Node> struct B2Codes { static constexpr uint32_t LEAF = OM_LEAF; typedef uint16_t stk_t; };
-template <> struct B2Codes<OmBvh2NodeW> { static constexpr uint32_t LEAF = OM_LEAFW; typedef uint32_t stk_t; };
+// ORDERED: the node is the ray-ordered LDS copy (OmBvh2NodeS, om_b2_planes.h), read per axis at the ray's sign.
+template <class Node> struct B2Codes { static constexpr uint32_t LEAF = OM_LEAF; typedef uint16_t stk_t; static constexpr bool ORDERED = false; };
+template <> struct B2Codes<OmBvh2NodeW> { static constexpr uint32_t LEAF = OM_LEAFW; typedef uint32_t stk_t; static constexpr bool ORDERED = false; };
+template <> struct B2Codes<OmBvh2NodeS> { static constexpr uint32_t LEAF = OM_LEAF; typedef uint16_t stk_t; static constexpr bool ORDERED = true; };
 // Plane P (lox loy loz hix hiy hiz) of child k of a 4-wide node, f32 or half.
 template <int P> __device__ __forceinline__ float b4p(const OmBvh4Node& N, int k) {
     return P == 0 ? N.lox[k] : P == 1 ? N.loy[k] : P == 2 ? N.loz[k] : P == 3 ? N.hix[k] : P == 4 ? N.hiy[k] : N.hiz[k];
@@ -785,24 +788,53 @@ __device__ __forceinline__ int traced_bvh2(const OmSceneDev& S, const Node* node
     const float t_lo = tmin * 0.5f - 1e-3f;
     offer_always2(S, o, d, tmin, ix, iy, iz, nox, noy, noz, t_lo, closest, best, w);
     if (Wk::ANY && best >= 0) return best;
+    uint32_t cur = 0;                                   // 16-bit code: node index | OM_LEAF + leaf index
+    // Ordered nodes (OmBvh2NodeS): per axis, the address of the ray's (near plane, far plane) pair
+    // of child 0 in slot 0 -- the dword the sign of the inverse direction picks in [lo, hi, lo].
+    // fmaf is monotone in the plane: with lo <= hi, fma(lo, ix, nox) <= fma(hi, ix, nox) for
+    // ix > 0 and the reverse for ix < 0 (inv_dir never returns 0 and keeps the sign of -0), so
+    // the pair read here gives (smin, smax) of the unordered form's two values up to the sign of
+    // a zero, which no compare sees; a NaN in either still reaches near or far and falls through
+    // to "visit".  h0, h1, swap, every push and every leaf visit are those of the unordered form.
+    // (tests/cpp/ordered_planes.cpp restates this read and the one in `slabs` on the host, index for
+    // index, to prove that: a change to the indices here is a change there.)
+    constexpr bool kOrdered = B2Codes<Node>::ORDERED;
+    const char *px = nullptr, *py = nullptr, *pz = nullptr;
+    if constexpr (kOrdered) {
+        static_assert(CUNIT == 16 && !HYB, "ordered nodes: LDS slots addressed in 16-B units");
+        px = (const char*)nodes + 4u * b2s_pair(0u, 0u, ix < 0.f ? 1u : 0u);
+        py = (const char*)nodes + 4u * b2s_pair(0u, 1u, iy < 0.f ? 1u : 0u);
+        pz = (const char*)nodes + 4u * b2s_pair(0u, 2u, iz < 0.f ? 1u : 0u);
+    }
     // slab tests of node N's two child boxes: -> h0, h1 (hit), and whether child 1 is nearer
     auto slabs = [&](const Node& N, bool& h0, bool& h1, bool& swap) {
         w.add_pre(2);
         const float t_hi = closest * 1.0001f + 1e-3f;
-        // half planes (OmBvh2NodeH): the (float) conversion folds into v_fma_mix_f32
-        float x0 = __builtin_fmaf(b2p<0>(N), ix, nox), x1 = __builtin_fmaf(b2p<3>(N), ix, nox);
-        float y0 = __builtin_fmaf(b2p<1>(N), iy, noy), y1 = __builtin_fmaf(b2p<4>(N), iy, noy);
-        float z0 = __builtin_fmaf(b2p<2>(N), iz, noz), z1 = __builtin_fmaf(b2p<5>(N), iz, noz);
-        const float n0 = slab_near(x0, x1, y0, y1, z0, z1, t_lo);
-        const float f0 = slab_far(x0, x1, y0, y1, z0, z1, t_hi);
-        x0 = __builtin_fmaf(b2p<6>(N), ix, nox); x1 = __builtin_fmaf(b2p<9>(N), ix, nox);
-        y0 = __builtin_fmaf(b2p<7>(N), iy, noy); y1 = __builtin_fmaf(b2p<10>(N), iy, noy);
-        z0 = __builtin_fmaf(b2p<8>(N), iz, noz); z1 = __builtin_fmaf(b2p<11>(N), iz, noz);
-        const float n1 = slab_near(x0, x1, y0, y1, z0, z1, t_lo);
-        const float f1 = slab_far(x0, x1, y0, y1, z0, z1, t_hi);
+        float n0, f0, n1, f1;
+        if constexpr (kOrdered) {
+            constexpr uint32_t k1 = b2s_pair(1u, 0u, 0u);       // child 1's pair: this many dwords on
+            const float* x = (const float*)(px + (cur << 4));
+            const float* y = (const float*)(py + (cur << 4));
+            const float* z = (const float*)(pz + (cur << 4));
+            n0 = smax3(__builtin_fmaf(x[0], ix, nox), __builtin_fmaf(y[0], iy, noy), smax(__builtin_fmaf(z[0], iz, noz), t_lo));
+            f0 = smin3(__builtin_fmaf(x[1], ix, nox), __builtin_fmaf(y[1], iy, noy), smin(__builtin_fmaf(z[1], iz, noz), t_hi));
+            n1 = smax3(__builtin_fmaf(x[k1], ix, nox), __builtin_fmaf(y[k1], iy, noy), smax(__builtin_fmaf(z[k1], iz, noz), t_lo));
+            f1 = smin3(__builtin_fmaf(x[k1 + 1u], ix, nox), __builtin_fmaf(y[k1 + 1u], iy, noy), smin(__builtin_fmaf(z[k1 + 1u], iz, noz), t_hi));
+        } else {
+            // half planes (OmBvh2NodeH): the (float) conversion folds into v_fma_mix_f32
+            float x0 = __builtin_fmaf(b2p<0>(N), ix, nox), x1 = __builtin_fmaf(b2p<3>(N), ix, nox);
+            float y0 = __builtin_fmaf(b2p<1>(N), iy, noy), y1 = __builtin_fmaf(b2p<4>(N), iy, noy);
+            float z0 = __builtin_fmaf(b2p<2>(N), iz, noz), z1 = __builtin_fmaf(b2p<5>(N), iz, noz);
+            n0 = slab_near(x0, x1, y0, y1, z0, z1, t_lo);
+            f0 = slab_far(x0, x1, y0, y1, z0, z1, t_hi);
+            x0 = __builtin_fmaf(b2p<6>(N), ix, nox); x1 = __builtin_fmaf(b2p<9>(N), ix, nox);
+            y0 = __builtin_fmaf(b2p<7>(N), iy, noy); y1 = __builtin_fmaf(b2p<10>(N), iy, noy);
+            z0 = __builtin_fmaf(b2p<8>(N), iz, noz); z1 = __builtin_fmaf(b2p<11>(N), iz, noz);
+            n1 = slab_near(x0, x1, y0, y1, z0, z1, t_lo);
+            f1 = slab_far(x0, x1, y0, y1, z0, z1, t_hi);
+        }
         h0 = !(n0 > f0); h1 = !(n1 > f1); swap = n1 < n0;
     };
-    uint32_t cur = 0;                                   // 16-bit code: node index | OM_LEAF + leaf index
     int sp = 0;                                         // lane stack: one entry per internal level
     // next entry off the stack -> cur; false when the stack is empty
     auto pop = [&]() -> bool {

@@ -158,6 +158,15 @@
 #ifndef OM_B2_NODE_STRIDE
 #define OM_B2_NODE_STRIDE 80
 #endif
+// BVH2 f32 nodes staged whole in LDS: 1, the LDS copy keeps every (child, axis) plane pair as
+// [lo, hi, lo] (om_b2_planes.h) and a lane reads (near, far) at the dword its ray's sign picks:
+// 4 min/max per box instead of 10, three more node addresses per visit.  Needs
+// the 80-B slot (a smaller OM_B2_NODE_STRIDE builds 0).  0: the node is copied as it is in memory
+// and the visit orders the planes.  The first launch keeps the plain node either way (TR_PLAIN_NODES,
+// om_wavefront.hip).  Measurements: DESIGN.md §8, profiles/ordered_planes/final_ab.txt.
+#ifndef OM_B2_PLANES
+#define OM_B2_PLANES 1
+#endif
 // Triangles + parallelograms (counted together; only the bounded ones with finite records) from
 // which select (om_bvh.cpp) puts them into the SBVH / BVH2 / BVH4 leaves beside the spheres and cubes
 // (DESIGN.md §5.17); a world with fewer keeps them in always2 and its frozen layout byte for byte.

@@ -70,6 +70,19 @@ static_assert(kB2Stride % 16u == 0u && kB2Stride >= sizeof(OmBvh2Node), "16-B al
 // stage_scene turns a child index into a slot offset in 16-B units (index * kB2Stride / 16): for
 // every tree the budget admits, the scaled code must still read as a node, not as a leaf
 static_assert(kB2LdsBudget / sizeof(OmBvh2Node) * (kB2Stride / 16u) < OM_LEAF, "scaled BVH2 child codes stay below OM_LEAF");
+// the staged node: the ray-ordered copy (om_b2_planes.h, OM_B2_PLANES) or the node as it is in memory
+// (a slot below 80 B, tools/ablate.sh p64, has no room for it and stages the plain node)
+constexpr bool kB2Planes = OM_B2_PLANES != 0 && kB2Stride >= sizeof(OmBvh2NodeS);
+using B2Staged = std::conditional<kB2Planes, OmBvh2NodeS, OmBvh2Node>::type;
+static_assert(kB2Stride >= sizeof(B2Staged), "the staged node fits its slot");
+// Variant flag of this file, above TR_BARY and dropped by tr_base like it: the kernel stages and
+// reads the plain node even with OM_B2_PLANES.  The first launch (k_bounce<FIRST>) sets it: the
+// three per-ray plane addresses of the ordered read are live over its traversals beside the
+// camera state and cost it 12 B of scratch per lane, for a gain of 1 % of that launch; with the
+// flag its code is the code it had (64 VGPRs, no scratch).
+constexpr int TR_PLAIN_NODES = 32;
+static_assert(TR_PLAIN_NODES > TR_BARY && (TR_PLAIN_NODES & (TR_BARY | (TR_BARY - 1))) == 0, "a flag of its own");
+constexpr bool b2_ordered(int trf) { return kB2Planes && (trf & TR_PLAIN_NODES) == 0; }
 // LDS bytes of the lane stack: S.b2_stack entries per lane (the tree's internal depth, 9 for
 // S-traced: 9 KiB per 512-lane workgroup instead of 24 KiB at the 24-entry bound).
 template <int TR>
@@ -238,7 +251,7 @@ __device__ __forceinline__ void store_path(const Queue& Q, uint64_t i, const Pat
 // the per-lane stack ([stack][nodes][leaf table]), or (TR_BVH2_GLOBAL) the breadth-first prefix
 // of the half-precision nodes in LDS and the rest read through L2.
 struct Tracer {
-    const OmBvh2Node* b2n;   // TR_BVH2_LDS: f32 nodes in LDS
+    const B2Staged* b2n;     // TR_BVH2_LDS: f32 nodes in LDS (ray-ordered with OM_B2_PLANES)
     const OmBvh2NodeH* h2l;  // TR_BVH2_GLOBAL: half nodes [0, nl) staged in LDS
     const OmBvh2NodeH* h2g;  //                 every half node, through L2
     uint32_t nl;
@@ -258,7 +271,7 @@ __device__ __forceinline__ Tracer stage_scene(const OmSceneDev& S) {   // every 
     constexpr int TR = tr_base(TRF);                                    // (staging does not depend on TR_BARY)
     Tracer t;
     t.stk = (uint16_t*)wf_lds + threadIdx.x;
-    t.b2n = S.b2nodes; t.b4n = S.b4nodes; t.bl = S.b2leaves; t.recs = S.srecs;
+    t.b2n = (const B2Staged*)S.b2nodes; t.b4n = S.b4nodes; t.bl = S.b2leaves; t.recs = S.srecs;
     t.h2l = S.b2h; t.h2g = S.b2h; t.nl = 0;
     t.h4l = S.b4h; t.h4g = S.b4h;
     t.w2l = wide_nodes(S); t.w2g = wide_nodes(S); t.stk32 = (uint32_t*)wf_lds + threadIdx.x;
@@ -293,17 +306,30 @@ __device__ __forceinline__ Tracer stage_scene(const OmSceneDev& S) {   // every 
         const uint32_t nn = (TR == TR_BVH2_LDS ? S.n_b2nodes : S.n_b4nodes) * wn;
         const uint4* sn = TR == TR_BVH2_LDS ? (const uint4*)S.b2nodes : (const uint4*)S.b4nodes;
         uint4* dst = wf_lds + STACKS * stack_bytes<TR>(S) / 16u;
-        for (uint32_t i = threadIdx.x; i < nn; i += kBlk) {
-            uint4 v = sn[i];
-            // BVH2 child codes (words 0 and 2: c0, c1) of internal nodes become slot offsets in
-            // 16-B units, so the traversal addresses a node with a shift (traced_bvh2's CUNIT)
-            if (TR == TR_BVH2_LDS && (i % wn) % 2u == 0u && v.w < OM_LEAF) v.w *= ws;
-            dst[(i / wn) * ws + i % wn] = v;
+        if constexpr (TR == TR_BVH2_LDS && b2_ordered(TRF)) {
+            // the node's 64 B into its slot by coalesced 16-B words, as below; then one node per
+            // thread and turn, in place (read whole, then written): every (child, axis) as
+            // [lo, hi, lo], the codes scaled as below (b2s_order)
+            for (uint32_t i = threadIdx.x; i < nn; i += kBlk) dst[(i / wn) * ws + i % wn] = sn[i];
+            __syncthreads();
+            for (uint32_t n = threadIdx.x; n < S.n_b2nodes; n += kBlk) {
+                OmBvh2NodeS* slot = (OmBvh2NodeS*)(dst + n * ws);
+                const OmBvh2Node raw = *(const OmBvh2Node*)slot;
+                *slot = b2s_order(raw, ws);
+            }
+        } else {
+            for (uint32_t i = threadIdx.x; i < nn; i += kBlk) {
+                uint4 v = sn[i];
+                // BVH2 child codes (words 0 and 2: c0, c1) of internal nodes become slot offsets in
+                // 16-B units, so the traversal addresses a node with a shift (traced_bvh2's CUNIT)
+                if (TR == TR_BVH2_LDS && (i % wn) % 2u == 0u && v.w < OM_LEAF) v.w *= ws;
+                dst[(i / wn) * ws + i % wn] = v;
+            }
         }
         uint32_t* ldst = (uint32_t*)(dst + nn / wn * ws);
         for (uint32_t i = threadIdx.x; i < S.n_b2leaves; i += kBlk) ldst[i] = S.b2leaves[i];
         __syncthreads();
-        t.b2n = (const OmBvh2Node*)dst; t.b4n = (const OmBvh4Node*)dst; t.bl = ldst;
+        t.b2n = (const B2Staged*)dst; t.b4n = (const OmBvh4Node*)dst; t.bl = ldst;
     }
     return t;
 }
@@ -320,8 +346,12 @@ __device__ __forceinline__ int trace_traced(const OmSceneDev& S, const Tracer& T
     if (TR == TR_BVH4_LDS) return traced_bvh4<kBlk>(S, T.b4n, T.bl, T.recs, T.stk, o, d, tmin, closest, w);
     if (TR == TR_BVH4_GLOBAL)
         return traced_bvh4<kBlk, Wk, true>(S, T.h4l, T.bl, T.recs, T.stk, o, d, tmin, closest, w, T.h4g, T.nl);
-    if (TR == TR_BVH2_LDS)
-        return traced_bvh2<kStackDepth, kBlk, Wk, false, OmBvh2Node, 16>(S, T.b2n, T.bl, T.recs, T.stk, o, d, tmin, closest, w);
+    if (TR == TR_BVH2_LDS) {
+        if constexpr (b2_ordered(TRF))
+            return traced_bvh2<kStackDepth, kBlk, Wk, false, OmBvh2NodeS, 16>(S, (const OmBvh2NodeS*)T.b2n, T.bl, T.recs, T.stk, o, d, tmin, closest, w);
+        else
+            return traced_bvh2<kStackDepth, kBlk, Wk, false, OmBvh2Node, 16>(S, (const OmBvh2Node*)T.b2n, T.bl, T.recs, T.stk, o, d, tmin, closest, w);
+    }
     if (TR == TR_BVH2_GLOBAL)
         return traced_bvh2<kStackDepth, kBlk, Wk, true>(S, T.h2l, T.bl, T.recs, T.stk, o, d, tmin, closest, w, T.h2g, T.nl);
     if (TR == TR_BVH2_WIDE)
@@ -466,7 +496,9 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
     __shared__ uint32_t q_next, q_out;
     if (threadIdx.x == 0) { q_next = kBlk / 64u; q_out = 0u; }
     __syncthreads();
-    const Tracer T = HIT ? Tracer{} : stage_scene<TR>(S);
+    // (FIRST: the plain staged nodes, TR_PLAIN_NODES above)
+    constexpr int TRS = FIRST ? (TR | TR_PLAIN_NODES) : TR;
+    const Tracer T = HIT ? Tracer{} : stage_scene<TRS>(S);
     const uint32_t cap = depth_cap(P);
     WorkT<COUNT, false, tr_bary(TR)> w;
     uint32_t segs = 0;
@@ -527,7 +559,7 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_bounce(OmSceneDev S, OmP
                     const float2 h = hitbuf[i];
                     closest = h.x; best = __float_as_int(h.y);
                 } else if (!(listed && sg == 0u)) {
-                    best = trace<TR, MARCH>(S, P, T, p.o, p.d, closest, w);
+                    best = trace<TRS, MARCH>(S, P, T, p.o, p.d, closest, w);
                 }
                 keep = shade_path<MARCH, USER>(S, P, cap, p, closest, best, res, res_id);
                 if (COUNT) segs++;

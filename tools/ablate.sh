@@ -104,6 +104,9 @@ declare -A V=(
   [p64]="$COMMON $DEV -DOM_B2_NODE_STRIDE=64"
   [p96]="$COMMON $DEV -DOM_B2_NODE_STRIDE=96"
   [p112]="$COMMON $DEV -DOM_B2_NODE_STRIDE=112"
+  # BVH2 nodes staged in LDS: ray-ordered plane pairs (default 1), or the node as it is in memory
+  [planes0]="$COMMON $DEV -DOM_B2_PLANES=0"
+  [planes1]="$COMMON $DEV -DOM_B2_PLANES=1"
   # LLVM AMDGPU scheduler strategies (same code, different instruction order)
   [ilp]="$COMMON $DEV -mllvm -amdgpu-sched-strategy=max-ilp"
   [memclause]="$COMMON $DEV -mllvm -amdgpu-sched-strategy=max-memory-clause"
