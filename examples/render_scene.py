@@ -8,6 +8,7 @@ the F12 save of main.rs:473-476.
     python examples/render_scene.py --width 1000 --height 666 --pick 500 400      # what is under a pixel
     python examples/render_scene.py --width 1000 --height 666 --ao 16 0.5         # ambient occlusion, out/ao.bmp
     python examples/render_scene.py --mesh model.obj --spp 64                     # a triangle mesh over the ground
+    python examples/render_scene.py --camera fisheye --spp 32                     # another camera model, out/fisheye.bmp
 """
 import argparse
 import os
@@ -76,6 +77,50 @@ def ambient_occlusion(frozen, cam, W, H, samples, radius, seed):
     return np.ascontiguousarray(np.repeat(grey.reshape(H, W, 1), 3, axis=2))
 
 
+def camera_rays(model, cam, W, H, device):
+    """(W*H, 6) float32 centre rays of another camera model, built on the device with torch, row-major:
+    fisheye (equidistant, 180 degrees across the frame's width), ortho (parallel rays over a 12-wide window) or
+    equirect (a 360 x 180 degree panorama), all at the camera's origin, looking along -w."""
+    import torch
+    r = cam.raw
+    t = lambda v: torch.tensor(list(v), dtype=torch.float32, device=device)
+    org, cu, cv, cw = t(r.origin), t(r.u_of_plane), t(r.v_of_plane), t(r.w_of_plane)
+    j, i = torch.meshgrid(torch.arange(H, dtype=torch.float32, device=device),
+                          torch.arange(W, dtype=torch.float32, device=device), indexing="ij")
+    x = ((i.reshape(-1) + 0.5) / W * 2.0 - 1.0)                    # -1 .. 1 left to right
+    y = (1.0 - (j.reshape(-1) + 0.5) / H * 2.0) * (H / W)          # up, same scale
+    o = org.expand(W * H, 3)
+    if model == "fisheye":
+        rad = torch.sqrt(x * x + y * y).clamp_min(1e-12)
+        theta = rad * (np.pi / 2.0)
+        s = torch.sin(theta) / rad
+        d = (x * s)[:, None] * cu + (y * s)[:, None] * cv - torch.cos(theta)[:, None] * cw
+    elif model == "ortho":
+        o = org + (6.0 * x)[:, None] * cu + (6.0 * y)[:, None] * cv
+        d = (-cw).expand(W * H, 3)
+    else:                                                           # equirect
+        lon, lat = x * np.pi, (1.0 - (j.reshape(-1) + 0.5) / H * 2.0) * (np.pi / 2.0)
+        d = (torch.cos(lat) * torch.sin(lon))[:, None] * cu + torch.sin(lat)[:, None] * cv \
+            - (torch.cos(lat) * torch.cos(lon))[:, None] * cw
+    d = d / torch.linalg.vector_norm(d, dim=1, keepdim=True)       # the unit-direction precondition
+    return torch.cat([o, d], dim=1).contiguous()
+
+
+def render_camera_model(frozen, cam, W, H, model, spp, max_depth, seed):
+    """Mean of spp ray_color calls (sample = 0 .. spp-1, stream = the pixel index) -> (H, W, 3) u8 with
+    the renderer's gamma (sqrt) and clamp."""
+    import torch
+    device = torch.device("cuda", int(frozen.device))
+    rays = camera_rays(model, cam, W, H, device)
+    acc = torch.zeros((W * H, 3), dtype=torch.float32, device=device)
+    out = torch.empty((W * H, 5), dtype=torch.float32, device=device)
+    for s in range(spp):
+        frozen.ray_color(rays, max_depth=max_depth, seed=seed, sample=s, out=out)
+        acc += out[:, :3]
+    rgb = (acc / spp).clamp_min(0.0).sqrt().clamp(0.0, 0.999) * 256.0
+    return np.ascontiguousarray(rgb.to(torch.uint8).reshape(H, W, 3).cpu().numpy())
+
+
 def mesh_scene(path):
     """random_scene's ground sphere with the OBJ mesh standing on it: scaled to height 2, centred in x
     and z, one material, added with one add_triangles call."""
@@ -115,6 +160,10 @@ def main():
     ap.add_argument("--ao", nargs=2, metavar=("SAMPLES", "RADIUS"),
                     help="write ao.bmp/ppm: ambient occlusion from SAMPLES any-hit rays of length RADIUS per primary hit "
                          "(FrozenHittableList.occluded), and exit (no render)")
+    ap.add_argument("--camera", choices=("fisheye", "ortho", "equirect"),
+                    help="render through another camera model instead of the thin lens: its rays are built on the device "
+                         "with torch and traced with FrozenHittableList.ray_color, --spp calls of one sample each; writes "
+                         "MODEL.bmp/ppm and exits")
     args = ap.parse_args()
 
     W, H = args.width, args.height
@@ -143,6 +192,16 @@ def main():
         print(f"{W}x{H} ambient occlusion, {samples} rays of length {radius} per hit point, in {time.perf_counter() - t0:.3f} s")
         os.makedirs(args.out, exist_ok=True)
         path = os.path.join(args.out, f"ao.{'ppm' if args.ppm else 'bmp'}")
+        (om.write_ppm if args.ppm else om.write_bmp)(path, rgb)
+        print("wrote", path)
+        return
+    if args.camera:
+        t0 = time.perf_counter()
+        rgb = render_camera_model(frozen, cam, W, H, args.camera, args.spp, args.max_depth, args.seed)
+        dt = time.perf_counter() - t0
+        print(f"{W}x{H}x{args.spp} {args.camera} in {dt:.3f} s ({W * H * args.spp / dt / 1e6:.0f} Mpaths/s)")
+        os.makedirs(args.out, exist_ok=True)
+        path = os.path.join(args.out, f"{args.camera}.{'ppm' if args.ppm else 'bmp'}")
         (om.write_ppm if args.ppm else om.write_bmp)(path, rgb)
         print("wrote", path)
         return

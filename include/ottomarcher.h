@@ -24,6 +24,7 @@
  *   om_camera_new         Camera::new                               camera.rs:38-59
  *   om_upload_world       HittableList::freeze -> FrozenHittableList  hits.rs:87-89, 116-185
  *   om_hit_rays*   FrozenHittableList::hit   hits.rs:270-334
+ *   om_ray_color*  ray_color                 render_thread.rs:128-143
  *   om_render / om_render_device   render_thread::render (all threads of main.rs:200-214)
  *                                                                   render_thread.rs:145-202
  *   om_pixel_stats        Pixel/Stats                               render_thread.rs:9-51
@@ -359,6 +360,57 @@ om_status om_hit_rays_windows(om_ctx* ctx, const om_query_params* q, const om_ra
  * stages the tree once and loops over blocks of OM_QUERY_BLOCK rays); 0 on error. */
 #define OM_QUERY_BLOCK 512
 uint32_t om_query_max_grid(om_ctx* ctx);
+/* ---- radiance queries: ray_color(ray, world, max_depth, tmin, tmax) (render_thread.rs:128-143) ----
+ * out[i] = ray_color(rays[i]) exactly as the renderer computes it for a camera ray: the bounce loop,
+ * scatter, sky and depth cap of om_render, entered with the caller's rays (another camera model,
+ * light probes, irradiance samples at surface points, one path from a picked point).
+ *   om_radiance  color: the path's colour, -0 on an exhausted depth; depth: the first segment's t,
+ *            +inf when it misses; obj: the first-hit id in the convention of om_hit / om_pixel_stats
+ *            (0 = the first segment missed).  Every record of a successful call is written.
+ *   om_path_params  tmin / tmax / march_steps / max_depth as in om_render_params (max_depth 0 and 1
+ *            both trace one segment).  The path of ray i draws from an om-rng v2 PathRng stream:
+ *            rng[i] when states are given, else the stream of (seed, pixel = stream_base + i mod
+ *            2^32, sample) from its start.
+ *   om_path_rng_state  the state of stream (seed, pixel, sample) after `draws` draws, low word the
+ *            Weyl counter, high word the key.  When om_render's sample reaches ray_color it has
+ *            consumed 2 jitter draws and 2 per try of the lens-disc rejection.  Host only, no ctx.
+ * The guarantee is bit-identity with the reference loop for every finite ray in the domain stated
+ * for om_hit_rays* above; segment 0 of a ray whose origin is beyond the slab test's reach runs the
+ * reference loop, as in om_hit_rays*.  The unit-direction precondition is that of om_ray.  A ray with
+ * a NaN or infinite component is not traced and does not disturb the other records: its record is
+ * colour (NaN, NaN, NaN), depth +inf, obj 0, and it counts no segment.
+ * Status codes follow om_hit_rays*: n == 0 is OM_OK and launches nothing; a null ctx, params, rays or
+ * out with n > 0, or a NaN tmin / tmax, is OM_ERR_INVALID; a call before om_upload_world is
+ * OM_ERR_STATE; a failed call writes nothing.  rays and out may have any 4-byte alignment, rng
+ * needs 8.  The query uses the ctx's kernel choice (om_set_kernel) and om_set_tail_bounce, and always
+ * runs the wavefront's queues and tails, whatever om_set_pipeline says (there is no megakernel
+ * form).  It shares the ctx's path queues with renders: one stream per ctx at a time.  With counting
+ * on, a call adds the segments it really traced and their prim_tests / pre_tests / march_steps;
+ * samples, credited and the om_progress word are untouched.  With om_set_timing on, a query's launches are
+ * timed in the render's classes (OM_KT_BOUNCE0, OM_KT_BOUNCE, OM_KT_TAIL; mode 2: OM_KT_BOUNCE_SPAN), so
+ * om_get_kernel_times sums renders and queries since the last read. */
+typedef struct om_path_params {
+    float tmin, tmax;
+    uint32_t march_steps;
+    uint32_t max_depth;
+    uint64_t seed;          /* om-rng v2 seed */
+    uint32_t stream_base;   /* rng NULL: ray i draws from the stream of pixel stream_base + i (mod 2^32) */
+    uint32_t sample;
+} om_path_params;           /* 32 B */
+typedef struct om_radiance { float color[3]; float depth; uint32_t obj; } om_radiance;   /* 20 B */
+uint64_t om_path_rng_state(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t draws);
+/* Device form: dev_rays / dev_rng / dev_out are device memory on ctx's device; asynchronous on
+ * `stream` (NULL = ctx's own stream). */
+om_status om_ray_color_device(om_ctx* ctx, const om_path_params* p, const om_ray* dev_rays,
+                              const uint64_t* dev_rng /* NULL: p's stream_base / sample */, uint32_t n,
+                              om_radiance* dev_out, void* stream);
+/* Host form, synchronous, staged like om_hit_rays. */
+om_status om_ray_color(om_ctx* ctx, const om_path_params* p, const om_ray* rays, const uint64_t* rng, uint32_t n,
+                       om_radiance* out);
+/* Paths per batch of a radiance query: 2^paths_log2, 6 .. 27; 0 = default (2^25, the renderer's batch).
+ * Larger calls run their batches one after another.  A pure scheduling knob: results are
+ * bit-identical for every value. */
+om_status om_set_path_batch(om_ctx* ctx, uint32_t paths_log2);
 /* Page-lock a caller-owned host buffer (e.g. the framebuffer) so om_render's copies run as
  * DMA at full PCIe speed; the buffer must stay allocated until om_host_unregister. */
 om_status om_host_register(void* p, size_t bytes);

@@ -378,6 +378,18 @@ public:
               ctx_);
         return occ;
     }
+    // ray_color (render_thread.rs:128-143) of a batch of caller-given rays: the renderer's bounce
+    // loop for any ray, one om_radiance (colour, first-hit depth, first-hit id) per ray, in order
+    // (om_ray_color).  Ray i draws from rng[i] (PathRng states, om_path_rng_state) or, with `rng`
+    // empty, from the stream (p.seed, p.stream_base + i, p.sample).
+    std::vector<om_radiance> ray_color(const std::vector<om_ray>& rays, const om_path_params& p,
+                                       const std::vector<uint64_t>& rng = {}) const {
+        if (!rng.empty() && rng.size() != rays.size()) throw Error(OM_ERR_INVALID, "ray_color: one rng state per ray");
+        std::vector<om_radiance> out(rays.size());
+        check(om_ray_color(ctx_, &p, rays.data(), rng.empty() ? nullptr : rng.data(), (uint32_t)rays.size(), out.data()), ctx_);
+        return out;
+    }
+    void set_path_batch(uint32_t paths_log2) { check(om_set_path_batch(ctx_, paths_log2), ctx_); }
 
 private:
     om_ctx* ctx_ = nullptr;

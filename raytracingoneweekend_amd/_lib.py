@@ -77,6 +77,18 @@ class om_ray_window(C.Structure):              # one [tmin, tmax] per ray, 8 B
     _fields_ = [("tmin", C.c_float), ("tmax", C.c_float)]
 
 
+class om_path_params(C.Structure):            # radiance queries (om_ray_color*), 32 B
+    _fields_ = [("tmin", C.c_float), ("tmax", C.c_float), ("march_steps", C.c_uint32), ("max_depth", C.c_uint32),
+                ("seed", C.c_uint64), ("stream_base", C.c_uint32), ("sample", C.c_uint32)]
+
+
+class om_radiance(C.Structure):                # ray_color's (colour, first-hit depth, first-hit id), 20 B
+    _fields_ = [("color", C.c_float * 3), ("depth", C.c_float), ("obj", C.c_uint32)]
+
+
+RADIANCE_DTYPE = np.dtype([("color", "<f4", (3,)), ("depth", "<f4"), ("obj", "<u4")])
+assert RADIANCE_DTYPE.itemsize == 20 and C.sizeof(om_radiance) == 20 and C.sizeof(om_path_params) == 32
+
 # numpy views of om_ray / om_hit / om_ray_window
 WINDOW_DTYPE = np.dtype([("tmin", "<f4"), ("tmax", "<f4")])
 RAY_DTYPE = np.dtype([("orig", "<f4", (3,)), ("dir", "<f4", (3,))])
@@ -135,6 +147,7 @@ EXPORTS = [
     "om_hit_rays_device", "om_hit_rays", "om_world_object_material", "om_query_max_grid",
     "om_occluded_rays_device", "om_occluded_rays", "om_hit_rays_windows_device", "om_hit_rays_windows",
     "om_world_add_triangles", "om_world_tree_info", "om_get_tree_info",
+    "om_path_rng_state", "om_ray_color_device", "om_ray_color", "om_set_path_batch",
 ]
 OM_COMM_ID_BYTES = 128
 OM_TRANSPORT_RCCL, OM_TRANSPORT_LOCAL = 0, 1
@@ -260,6 +273,10 @@ def _load():
         "om_hit_rays_windows": (st, [vp, C.POINTER(om_query_params), vp, vp, C.c_uint32, vp]),
         "om_world_tree_info": (st, [vp, C.POINTER(om_tree_info)]),
         "om_get_tree_info": (st, [vp, C.POINTER(om_tree_info)]),
+        "om_path_rng_state": (C.c_uint64, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "om_ray_color_device": (st, [vp, C.POINTER(om_path_params), vp, vp, C.c_uint32, vp, vp]),
+        "om_ray_color": (st, [vp, C.POINTER(om_path_params), vp, vp, C.c_uint32, vp]),
+        "om_set_path_batch": (st, [vp, C.c_uint32]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

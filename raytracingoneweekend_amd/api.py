@@ -24,12 +24,20 @@ from ._lib import check, f3, fptr, lib
 __all__ = [
     "Material", "Mat4x4", "m4x4", "Camera", "Sphere", "Cube", "Triangle", "Parallelogram", "InfinitePlane",
     "MarchedSphere", "MarchedBox", "MarchedTorus", "MarchedSdf", "HittableList", "FrozenHittableList", "PixelsBox", "render",
-    "RenderStats", "HitRecord", "HIT_DTYPE", "RAY_DTYPE", "WINDOW_DTYPE",
+    "RenderStats", "HitRecord", "HIT_DTYPE", "RAY_DTYPE", "WINDOW_DTYPE", "RADIANCE_DTYPE", "path_rng_state",
 ]
 
 HIT_DTYPE = L.HIT_DTYPE     # om_hit: t, point, normal, obj (hits.rs:11-17)
 RAY_DTYPE = L.RAY_DTYPE     # om_ray: orig, dir (ray.rs:5-8)
 WINDOW_DTYPE = L.WINDOW_DTYPE   # om_ray_window: tmin, tmax of one ray
+RADIANCE_DTYPE = L.RADIANCE_DTYPE   # om_radiance: color, depth, obj (ray_color's triple, render_thread.rs:128-143)
+
+
+def path_rng_state(seed, pixel, sample, draws=0):
+    """State of the om-rng v2 path stream (seed, pixel, sample) after `draws` draws (om_path_rng_state):
+    low word the Weyl counter, high word the key.  om_render's sample has drawn 2 + 2 * (lens-disc
+    tries) times when ray_color starts."""
+    return int(lib.om_path_rng_state(int(seed), int(pixel) & 0xFFFFFFFF, int(sample) & 0xFFFFFFFF, int(draws) & 0xFFFFFFFF))
 
 
 # ---------------------------------------------------------------- materials.rs
@@ -512,6 +520,92 @@ class FrozenHittableList:
             check(lib.om_hit_rays(self._ctx, C.byref(q), a.ctypes.data_as(C.c_void_p), n, hits.ctypes.data_as(C.c_void_p)),
                   self._ctx)
         return hits
+
+    def set_path_batch(self, paths_log2):
+        """Paths per batch of ray_color: 2^paths_log2 (6..27; 0 = default), a pure scheduling knob
+        (om_set_path_batch)."""
+        check(lib.om_set_path_batch(self._ctx, int(paths_log2)), self._ctx)
+
+    def ray_color(self, rays, max_depth=50, tmin=0.001, tmax=100.0, march_steps=1024, seed=1, stream_base=0, sample=0,
+                  rng=None, out=None, stream=None):
+        """ray_color (render_thread.rs:128-143) of a batch of caller-given rays: the renderer's bounce
+        loop entered with any ray (om_ray_color / om_ray_color_device).
+
+        `rays` as for hit_rays.  numpy in -> an n-vector of RADIANCE_DTYPE (color, depth = the first
+        segment's t or inf, obj = the first-hit id or 0), synchronous.  A torch ROCm tensor in -> an
+        (n, 5) float32 tensor of om_radiance records on the device (column 4 holds the obj bits),
+        asynchronous, with the stream rules of hit_rays.
+        The path of ray i draws from `rng[i]` (uint64 PathRng states, path_rng_state; a numpy array
+        with numpy rays, an int64 tensor on the rays' device with torch rays) or, by default, from the
+        stream (seed, stream_base + i mod 2^32, sample) from its start.  Callers that want several
+        samples per ray repeat the call with another `sample`."""
+        what = "ray_color"
+        p = L.om_path_params(float(tmin), float(tmax), int(march_steps), int(max_depth), int(seed),
+                             int(stream_base) & 0xFFFFFFFF, int(sample) & 0xFFFFFFFF)
+        if type(rays).__module__.split(".")[0] == "torch":
+            import torch
+            if not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 6 \
+                    or not rays.is_contiguous():
+                raise ValueError(f"{what}: need a contiguous (n, 6) float32 tensor on the device")
+            if rays.device.index != int(self.device):
+                raise ValueError(f"{what}: rays are on {rays.device}, the world is on device {self.device}")
+            n = rays.shape[0]
+            if rng is not None:
+                if type(rng).__module__.split(".")[0] != "torch" or not rng.is_cuda or rng.dtype != torch.int64 \
+                        or tuple(rng.shape) != (n,) or not rng.is_contiguous() or rng.device != rays.device:
+                    raise ValueError(f"{what}: rng must be a contiguous (n,) int64 tensor on the rays' device")
+            if out is None:
+                out = torch.empty((n, 5), dtype=torch.float32, device=rays.device)
+            elif type(out).__module__.split(".")[0] != "torch" or not out.is_cuda or out.dtype != torch.float32 \
+                    or tuple(out.shape) != (n, 5) or not out.is_contiguous() or out.device != rays.device:
+                raise ValueError(f"{what}: out must be a contiguous (n, 5) float32 tensor on the rays' device")
+            if stream is not None and int(stream) == 0:
+                raise ValueError(f"{what}: stream 0 is the ctx's own stream to the library; pass a stream or none")
+            cur = side = None
+            if stream is None:
+                cur = torch.cuda.current_stream(rays.device)
+                stream = cur.cuda_stream
+                if stream == 0:                                   # torch's null stream: order a side stream with it
+                    if getattr(self, "_torch_side", None) is None:
+                        self._torch_side = torch.cuda.Stream(device=rays.device)
+                    side = self._torch_side
+                    side.wait_stream(cur)
+                    stream = side.cuda_stream
+            rp = C.c_void_p(rng.data_ptr()) if rng is not None else None
+            try:
+                check(lib.om_ray_color_device(self._ctx, C.byref(p), C.c_void_p(rays.data_ptr()), rp, n,
+                                              C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
+            finally:
+                if side is not None:
+                    rays.record_stream(side)
+                    out.record_stream(side)
+                    if rng is not None:
+                        rng.record_stream(side)
+                    cur.wait_stream(side)
+            return out
+        a = np.ascontiguousarray(rays)
+        if a.dtype == L.RAY_DTYPE:
+            a = a.reshape(-1)
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 6:
+                raise ValueError(f"{what}: need an (n, 6) float32 array")
+        n = a.shape[0]
+        rp = None
+        if rng is not None:
+            if type(rng).__module__.split(".")[0] == "torch":
+                raise ValueError(f"{what}: numpy rays need numpy rng states")
+            r = np.ascontiguousarray(rng, dtype=np.uint64)
+            if r.shape != (n,):
+                raise ValueError(f"{what}: rng must hold one uint64 state per ray")
+            rp = r.ctypes.data_as(C.c_void_p)
+        if out is None:
+            out = np.empty(n, dtype=L.RADIANCE_DTYPE)
+        elif not isinstance(out, np.ndarray) or out.dtype != L.RADIANCE_DTYPE or out.shape != (n,) or not out.flags.c_contiguous:
+            raise ValueError(f"{what}: out must be a contiguous n-vector of RADIANCE_DTYPE")
+        check(lib.om_ray_color(self._ctx, C.byref(p), a.ctypes.data_as(C.c_void_p), rp, n, out.ctypes.data_as(C.c_void_p)),
+              self._ctx)
+        return out
 
     def query_max_grid(self):
         """Workgroups of the largest query launch on this device (om_query_max_grid)."""

@@ -26,6 +26,7 @@ using namespace omd;
 static_assert(sizeof(om_pixel_stats) == 40, "om_pixel_stats layout");
 static_assert(sizeof(om_ray) == 24 && sizeof(om_hit) == 32 && sizeof(om_query_params) == 16, "query record layouts");
 static_assert(sizeof(om_ray_window) == 8, "query window layout");
+static_assert(sizeof(om_path_params) == 32 && sizeof(om_radiance) == 20, "radiance query layouts");
 static_assert(OM_QUERY_BLOCK == 512, "OM_QUERY_BLOCK is the wavefront workgroup size");
 static_assert(sizeof(OmAffineTest) == 64 && sizeof(OmBvhNode) == 32, "layout");
 static_assert(sizeof(OmBvh2NodeW) == sizeof(OmBvh2NodeH) && sizeof(om_tree_info) == 32, "wide node / om_tree_info layout");
@@ -81,6 +82,8 @@ struct om_ctx {
     DevBuf frame_list;                  // tile-ordered pixel list of the full frame (wavefront path)
     DevBuf query_rays, query_hits;      // om_hit_rays staging (grown on demand, reused)
     DevBuf query_windows, query_occ;    // om_*_windows / om_occluded_rays staging
+    DevBuf path_rng, path_out;          // om_ray_color staging (the rays go through query_rays)
+    uint32_t path_batch_log2 = 0;       // om_set_path_batch (0 = default)
     uint32_t frame_w = 0, frame_h = 0;
     ~om_ctx() {
         for (auto& b : scene_bufs) b.release();
@@ -88,6 +91,7 @@ struct om_ctx {
         counters.release(); stats.release(); pixels.release(); frame_list.release();
         query_rays.release(); query_hits.release();
         query_windows.release(); query_occ.release();
+        path_rng.release(); path_out.release();
         view_scratch.release(); view_rgb.release(); tile_off.release(); tile_idx.release(); tile_tnear.release();
         wf.release();
         timer.release();
@@ -570,6 +574,88 @@ om_status om_occluded_rays_device(om_ctx* c, const om_query_params* q, const om_
 om_status om_occluded_rays(om_ctx* c, const om_query_params* q, const om_ray* rays, const om_ray_window* windows, uint32_t n,
                            uint8_t* occluded) {
     return host_query(c, q, rays, windows, n, nullptr, occluded);
+}
+
+// ---- radiance queries (ray_color, render_thread.rs:128-143) ----
+// om-rng v2 on the host: mix64 and the path key as om_device.h / launch() have them
+static uint64_t host_mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+uint64_t om_path_rng_state(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t draws) {
+    const uint64_t skey = host_mix64(seed + 0x632BE59BD9B4E019ULL);
+    const uint64_t z = host_mix64((((uint64_t)pixel << 32) | (uint64_t)sample) ^ skey);
+    // a draw adds the Weyl constant to the low word (mod 2^32) and leaves the key
+    const uint32_t s = (uint32_t)z + draws * 0x9E3779B9u;
+    return (z & 0xFFFFFFFF00000000ULL) | (uint64_t)s;
+}
+
+static om_status validate_paths(om_ctx* c, const om_path_params* p, const void* rays, uint32_t n, const void* out) {
+    if (!c) return set_err(nullptr, OM_ERR_INVALID, "om_ray_color: null ctx");
+    if (!p) return set_err(c, OM_ERR_INVALID, "om_ray_color: null params");
+    if (std::isnan(p->tmin) || std::isnan(p->tmax)) return set_err(c, OM_ERR_INVALID, "om_ray_color: tmin/tmax is NaN");
+    if (!c->have_world) return set_err(c, OM_ERR_STATE, "om_upload_world must precede radiance queries");
+    if (n && (!rays || !out)) return set_err(c, OM_ERR_INVALID, "om_ray_color: null rays/out");
+    return OM_OK;
+}
+
+om_status om_ray_color_device(om_ctx* c, const om_path_params* p, const om_ray* dev_rays, const uint64_t* dev_rng, uint32_t n,
+                              om_radiance* dev_out, void* stream) {
+    om_status s = validate_paths(c, p, dev_rays, n, dev_out);
+    if (s) return s;
+    if (n == 0) return OM_OK;
+    if (dev_rng && ((uintptr_t)dev_rng & 7u)) return set_err(c, OM_ERR_INVALID, "om_ray_color: rng must be 8-byte aligned");
+    OM_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (!c->counters.p) {
+        if ((s = ensure(c, c->counters, OMC_SLOTS * sizeof(unsigned long long))) != OM_OK) return s;
+        OM_HIP(c, hipMemsetAsync(c->counters.p, 0, OMC_SLOTS * sizeof(unsigned long long), st));
+    }
+    c->last_stream = st;
+    int mode = c->kernel;
+    if (mode == OM_KERNEL_AUTO) mode = OM_KERNEL_BVH2;
+    omw::PathQuery Q{};
+    Q.S = c->scene;
+    Q.P.tmin = p->tmin; Q.P.tmax = p->tmax; Q.P.march_steps = p->march_steps; Q.P.max_depth = p->max_depth;
+    Q.P.skey = host_mix64(p->seed + 0x632BE59BD9B4E019ULL);
+    Q.rays = dev_rays; Q.rng = dev_rng; Q.n = n; Q.stream_base = p->stream_base; Q.sample = p->sample; Q.out = dev_out;
+    Q.counters = (unsigned long long*)c->counters.p;
+    Q.count = c->count_work;
+    Q.trace_mode = wf_trace_mode(mode);
+    Q.tail_bounce = c->tail_bounce;
+    Q.paths_log2 = c->path_batch_log2;
+    Q.timer = &c->timer;
+    std::string err;
+    const hipError_t e = omw::ray_color(c->wf, Q, st, err);
+    if (e != hipSuccess) return set_err(c, OM_ERR_DEVICE, err + ": " + hipGetErrorString(e));
+    return OM_OK;
+}
+
+om_status om_ray_color(om_ctx* c, const om_path_params* p, const om_ray* rays, const uint64_t* rng, uint32_t n, om_radiance* out) {
+    om_status s = validate_paths(c, p, rays, n, out);
+    if (s) return s;
+    if (n == 0) return OM_OK;
+    OM_HIP(c, hipSetDevice(c->device));
+    if ((s = ensure(c, c->query_rays, (size_t)n * sizeof(om_ray))) != OM_OK) return s;
+    if (rng && (s = ensure(c, c->path_rng, (size_t)n * sizeof(uint64_t))) != OM_OK) return s;
+    if ((s = ensure(c, c->path_out, (size_t)n * sizeof(om_radiance))) != OM_OK) return s;
+    OM_HIP(c, hipMemcpyAsync(c->query_rays.p, rays, (size_t)n * sizeof(om_ray), hipMemcpyHostToDevice, c->stream));
+    if (rng) OM_HIP(c, hipMemcpyAsync(c->path_rng.p, rng, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    s = om_ray_color_device(c, p, (const om_ray*)c->query_rays.p, rng ? (const uint64_t*)c->path_rng.p : nullptr, n,
+                            (om_radiance*)c->path_out.p, c->stream);
+    if (s != OM_OK) return s;
+    OM_HIP(c, hipMemcpyAsync(out, c->path_out.p, (size_t)n * sizeof(om_radiance), hipMemcpyDeviceToHost, c->stream));
+    OM_HIP(c, hipStreamSynchronize(c->stream));
+    return OM_OK;
+}
+
+om_status om_set_path_batch(om_ctx* c, uint32_t paths_log2) {
+    if (!c) return set_err(nullptr, OM_ERR_INVALID, "null ctx");
+    if (paths_log2 != 0u && (paths_log2 < 6u || paths_log2 > (uint32_t)OM_WF_MAX_PATHS_LOG2))
+        return set_err(c, OM_ERR_INVALID, "om_set_path_batch: paths_log2 must be 0 or 6..27");
+    c->path_batch_log2 = paths_log2;
+    return OM_OK;
 }
 
 uint32_t om_query_max_grid(om_ctx* c) {

@@ -39,6 +39,11 @@
 #ifndef OM_WF_MIN_PATHS_LOG2
 #define OM_WF_MIN_PATHS_LOG2 25
 #endif
+// radiance queries (om_ray_color*): default paths per batch, 2^25 as ottomarcher.h documents it
+// (om_set_path_batch).  The render's batch floor above has the same value today; the two are tuned apart.
+#ifndef OM_WF_QUERY_PATHS_LOG2
+#define OM_WF_QUERY_PATHS_LOG2 25
+#endif
 // A BVH2 too big for LDS (S-10k: 107 KB of half nodes) stages its breadth-first prefix, up to this
 // many bytes of nodes, into LDS; deeper nodes are read through L2 (0 = every node from L2).  C3 with
 // half nodes (r04_ab5/ab6): 8 / 12 / 16 / 20 / 24 / 28 KB -> 4113 / 4137 / 4135 / 4067 / 4069 / 3676.

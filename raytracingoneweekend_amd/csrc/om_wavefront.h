@@ -111,6 +111,26 @@ void with_flags(const bool (&b)[N], F&& f, C... c) {
     else with_flags(b, f, c..., std::false_type{});
 }
 
+// One radiance query (om_ray_color*_device): ray_color of n caller-given rays through
+// the wavefront's queues, tails and schedule knobs.
+struct PathQuery {
+    OmSceneDev S;
+    OmParamsDev P;               // tmin, tmax, march_steps, max_depth, skey; the rest 0
+    const om_ray* rays;          // device, n records
+    const uint64_t* rng;         // device, n PathRng states; null: (skey, stream_base + i, sample)
+    uint32_t n;
+    uint32_t stream_base, sample;
+    om_radiance* out;            // device, n records
+    unsigned long long* counters;
+    bool count;
+    int trace_mode;              // as Launch::trace_mode
+    uint32_t tail_bounce;        // as Launch::tail_bounce
+    uint32_t paths_log2;         // log2 of the paths per batch (0 = 2^25, the renderer's)
+    Timer* timer;
+};
+// Queues the batches of Q on `stream`, through queue set 0 of B.
+hipError_t ray_color(Buffers& B, const PathQuery& Q, hipStream_t stream, std::string& err);
+
 // One batch of ray queries: closest-hit (om_hit_rays*_device) when `occluded` is
 // null, any-hit (om_occluded_rays_device, §5.16) otherwise.
 struct Query {

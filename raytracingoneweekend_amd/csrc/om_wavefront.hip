@@ -204,6 +204,15 @@ struct Gen {
     const float* tile_tnear;
 };
 
+// Path source of a ray_color batch (k_paths): the caller's rays and RNG states, from the batch's
+// first path on.
+struct RaySrc {
+    const om_ray* rays;
+    const uint64_t* rng;         // PathRng states (low word s, high word k); null: path_rng(skey, stream0 + i, sample)
+    uint32_t n;                  // paths of the batch
+    uint32_t stream0, sample;
+};
+
 // A path between bounces: ray_color's loop state (render_thread.rs:128-143).
 struct Path {
     F3 o, d, cur;
@@ -1126,6 +1135,122 @@ __global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_occluded(OmSceneDev S, O
     }
 }
 
+// ---------------------------------------------------------------- path queries
+// k_paths: segment 0 of ray_color (render_thread.rs:128-143) for the caller's rays of one batch
+// (om_ray_color*): bounce 0 of the wavefront with (rays[i], rng state) in the place
+// of gen_path.  The batch's 64-path blocks are dealt over the workgroups as bounce 0 deals camera
+// samples (batch_deal), a path's result slot is its index in the batch, and the survivors are
+// compacted into segment s of `out`, bounce 1's queue, by k_bounce's ballot and LDS counters; the
+// per-bounce launches and the tails take them from there unchanged.  There are no tile lists and no
+// fused second segment: these are not camera rays, and a wave of them is no 8x8 tile.
+// A ray can be any ray.  A lane whose origin is beyond the slab test's reach (far_origin) runs the
+// reference loop for segment 0, as in query_rays.  A ray with a NaN or infinite component is not
+// traced at all: its path ends here with the record (colour NaN, depth +inf, obj 0) and counts no
+// segment.  Such a path would stay non-finite in every later segment, and in a world with a
+// MarchedBox each of them can cost 2^22 SDF evaluations: the box's sdf of a NaN point is <= 0 (fmaxf /
+// fminf drop the NaN, as f32::max / min do: len(max(q, 0)) = 0, min(max(q.x, q.y, q.z), 0) <= 0), so
+// unstuck's loop (hits.rs:360-363, endless in the reference) runs to march_begin's safety cap.  One
+// garbage ray would then hold the device for max_depth times that.  Marched worlds march segment 0
+// here (march(), as k_query<., MARCH>), and their survivors go to the marched tail or the k_march launches.
+// The RNG state of path i is rng[i] (low word the Weyl counter, high word the key) or, with rng
+// null, path_rng(P.skey, stream0 + i, sample): a pixel index that wraps mod 2^32.
+template <int TR, bool COUNT, bool MARCH, bool USER>
+__global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_paths(OmSceneDev S, OmParamsDev P, Seg G, RaySrc R, Queue out,
+                                                uint32_t* __restrict__ count_out, float4* __restrict__ res,
+                                                uint32_t* __restrict__ res_id, unsigned long long* __restrict__ counters,
+                                                uint32_t* __restrict__ tail_next) {
+    // the traced tail's claim counter, as k_bounce<FIRST> zeroes it
+    if (tail_next && blockIdx.x == 0 && threadIdx.x == 0) *tail_next = 0u;
+    const uint64_t seg0 = (uint64_t)blockIdx.x * G.segcap;
+    const Deal dl = batch_deal(R.n, G.nseg);
+    const uint32_t chunks = dl.blocks_of(blockIdx.x);
+    if (chunks == 0) {
+        if (threadIdx.x == 0) count_out[blockIdx.x] = 0u;
+        return;
+    }
+    __shared__ uint32_t q_next, q_out;
+    if (threadIdx.x == 0) { q_next = kBlk / 64u; q_out = 0u; }
+    __syncthreads();
+    const Tracer T = stage_scene<TR>(S);
+    const uint32_t cap = depth_cap(P);
+    WorkT<COUNT, false, tr_bary(TR)> w;
+    uint32_t segs = 0;
+    const uint32_t lane = __lane_id();
+    for (uint32_t chunk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); chunk < chunks;) {   // wave-uniform
+        // (a batch has at most 2^OM_WF_MAX_PATHS_LOG2 paths: the index fits 32 bits)
+        const uint32_t i = (uint32_t)(dl.block(blockIdx.x, chunk) * 64u) + lane;
+        bool keep = false;
+        Path p;
+        bool live = i < R.n;
+        if (live) {
+            load_query_ray(R.rays, i, p.o, p.d);
+            // (per component, x * 0 is 0 or NaN: finite components whose sum would overflow stay finite rays)
+            if (!(p.o.x * 0.0f + p.o.y * 0.0f + p.o.z * 0.0f + p.d.x * 0.0f + p.d.y * 0.0f + p.d.z * 0.0f == 0.0f)) {   // not traced (above)
+                const float qnan = __uint_as_float(0x7FC00000u);
+                res[i] = make_float4(qnan, qnan, qnan, INFINITY);
+                res_id[i] = 0u;
+                live = false;
+            }
+        }
+        if (live) {
+            if (R.rng) {
+                const uint32_t* st = (const uint32_t*)(R.rng + i);
+                p.g.s = __builtin_nontemporal_load(st); p.g.k = __builtin_nontemporal_load(st + 1);
+            } else {
+                p.g = path_rng(P.skey, R.stream0 + i, R.sample);
+            }
+            p.cur = f3(1.0f, 1.0f, 1.0f); p.depthf = 0.0f; p.first_id = 0u; p.seg = 0u; p.slot = i;
+            float closest = P.tmax;
+            int best;
+            if (far_origin(S, p.o))
+                best = traced_brute<false>(S, p.o, p.d, P.tmin, closest, w);
+            else
+                best = trace_traced<TR>(S, T, p.o, p.d, P.tmin, closest, w);
+            if (MARCH) {                                             // trace<TR, true>'s march, once for both branches
+                float tm;
+                const int mg = march(S, p.o, p.d, P.tmin, P.tmax, closest, P.march_steps, tm, w);
+                if (mg >= 0) { best = mg; closest = tm; }
+            }
+            keep = shade_path<MARCH, USER>(S, P, cap, p, closest, best, res, res_id);
+            if (COUNT) segs++;
+        }
+        const uint64_t m = __ballot(keep);
+        uint32_t obase = 0u, nc = 0u;
+        if (lane == 0) {
+            obase = m ? atomicAdd(&q_out, (uint32_t)__popcll(m)) : 0u;
+            nc = atomicAdd(&q_next, 1u);
+        }
+        obase = __builtin_amdgcn_readfirstlane(obase);
+        chunk = __builtin_amdgcn_readfirstlane(nc);
+        const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (keep) store_path(out, seg0 + obase + rank, p);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) count_out[blockIdx.x] = q_out;
+    if (COUNT) {
+        flush_counter(counters, OMC_SEGMENTS, segs);
+        flush_counter(counters, OMC_PRIM_TESTS, w.prim);
+        flush_counter(counters, OMC_PRE_TESTS, w.pre);
+        flush_counter(counters, OMC_MARCH, w.march);
+    }
+}
+
+// k_radiance: res[i], res_id[i] of a finished batch -> out[i] (om_radiance, 20 B).  A 20-B record
+// is 16-B aligned only at every fourth index, so there is no vector store per record as
+// store_query_hit has for its 32-B hits: each field is one non-temporal dword store, for any 4-B
+// alignment of `out` (a wave's five stores cover 1280 contiguous bytes).
+__global__ __launch_bounds__(256) void k_radiance(const float4* __restrict__ res, const uint32_t* __restrict__ res_id,
+                                                  uint32_t n, om_radiance* __restrict__ out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 r = ld4(res + i);
+    const uint32_t id = __builtin_nontemporal_load(res_id + i);
+    float* o = (float*)(out + i);
+    __builtin_nontemporal_store(r.x, o); __builtin_nontemporal_store(r.y, o + 1); __builtin_nontemporal_store(r.z, o + 2);
+    __builtin_nontemporal_store(r.w, o + 3);
+    __builtin_nontemporal_store(__uint_as_float(id), o + 4);
+}
+
 // ---------------------------------------------------------------- accumulate
 // Adaptive batches (ad.list): lane kk owns live-list entry kk, and a pixel that is still live after
 // the batch, with samples of the call left, is appended to the stream's next list (one ballot and
@@ -1308,9 +1433,12 @@ inline uint32_t count_rows(uint32_t depth_cap) { return std::max<uint32_t>(depth
 // returns the number of bounce-family launches.
 // EXACT (marched worlds, where exact_view_built<TR>()): the marched set has C2's shape and no user
 // object (OmMSdf), so the march kernels take MarchedC2Lds and the shade leaves the SDF programs out.
+// X (ray_color batches): segment 0 is k_paths over the caller's rays instead of the camera's launch
+// (k_raygen and bounce 0's k_march pair, or k_bounce<FIRST> with its fused bounce 1); its out queue
+// is bounce 1's, and everything from there on is the render's.  R is then unused by the kernels.
 template <int TR, bool COUNT, bool MARCH, bool EXACT>
 uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Gen& R, uint32_t tail_at, uint32_t lds,
-                   uint32_t tail_grid) {
+                   uint32_t tail_grid, const RaySrc* X = nullptr) {
     constexpr int VIEW = EXACT && exact_view_built<TR>() ? MV_EXACT_C2_LDS : MV_ARRAYS;
     Timer& tm = *L.timer;
     const bool each = tm.mode == 1;
@@ -1337,11 +1465,15 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
         // buffer and k_bounce<HIT> shades and compacts
         {
             const int ti = each ? tm.begin(st) : -1;
-            hipLaunchKernelGGL((k_raygen<COUNT>), dim3(G.nseg), dim3(kBlk), 0, st, L.P, G, R, queue(B, 0), B.counts, B.res_id);
+            if (X)
+                hipLaunchKernelGGL((k_paths<TR, COUNT, true, !EXACT>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, *X, queue(B, 1),
+                                   B.counts + G.nseg, B.res, B.res_id, L.counters, (uint32_t*)nullptr);
+            else
+                hipLaunchKernelGGL((k_raygen<COUNT>), dim3(G.nseg), dim3(kBlk), 0, st, L.P, G, R, queue(B, 0), B.counts, B.res_id);
             tm.end(ti, OM_KT_BOUNCE0, st);
             ++launches;
         }
-        for (uint32_t bounce = 0; bounce < cap; ++bounce) {
+        for (uint32_t bounce = X ? 1u : 0u; bounce < cap; ++bounce) {
             const Queue in = queue(B, bounce & 1u), out = queue(B, (bounce + 1u) & 1u);
             const uint32_t* cin = B.counts + (size_t)bounce * G.nseg;
             if (bounce >= tail_at) return tail(in, cin);   // (tail_at 0: k_raygen's camera paths too)
@@ -1362,13 +1494,16 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
     // (fused first launch: bounces 0 and 1, its out queue is bounce 2's; the first queue the tail or a
     // per-bounce launch can read is the one that launch wrote, whatever tail_at asks for)
     for (uint32_t bounce = 0, next; bounce < cap; bounce = next) {
-        next = bounce + (bounce == 0 && kFuseB1 ? 2u : 1u);
+        next = bounce + (bounce == 0 && kFuseB1 && !X ? 2u : 1u);
         const Queue in = queue(B, bounce & 1u), out = queue(B, next & 1u);
         const uint32_t* cin = B.counts + (size_t)bounce * G.nseg;
         if (bounce > 0 && bounce >= tail_at) return tail(in, cin);
         uint32_t* cout = B.counts + (size_t)next * G.nseg;
         const int ti = each ? tm.begin(st) : -1;
-        if (bounce == 0)
+        if (bounce == 0 && X)
+            hipLaunchKernelGGL((k_paths<TR, COUNT, false, false>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, *X, out, cout,
+                               B.res, B.res_id, L.counters, tail_next);
+        else if (bounce == 0)
             hipLaunchKernelGGL((k_bounce<TR, COUNT, MARCH, true>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, R, in,
                                cin, out, cout, B.res, B.res_id, L.counters, (const float2*)nullptr, tail_next);
         else
@@ -1653,6 +1788,70 @@ hipError_t render(Buffers& B, const Launch& L, hipStream_t st, std::string& err)
     for (uint32_t k = 1; k < ns; ++k) {
         (void)hipEventRecord(B.ev[k], streams[k]);
         (void)hipStreamWaitEvent(st, B.ev[k], 0);
+    }
+    tm.end(call_ti, OM_KT_BOUNCE_SPAN, st, launches);
+    return hipSuccess;
+}
+
+// ray_color for Q.n caller-given rays (om_ray_color*): batches of at most
+// 2^paths_log2 paths, one after another on `st` through queue set 0 of the ctx (the set renders on
+// `st` use, so a query and a render of one ctx order themselves on the stream).  Per batch: k_paths
+// (segment 0), the render's per-bounce launches and tail (run_batch), k_radiance into the caller's
+// records.  The tail threshold is the render's without the fused first launch's extra bounce.
+hipError_t ray_color(Buffers& B, const PathQuery& Q, hipStream_t st, std::string& err) {
+    if (Q.n == 0) return hipSuccess;
+    const uint32_t log2 = Q.paths_log2 ? Q.paths_log2 : (uint32_t)OM_WF_QUERY_PATHS_LOG2;
+    const uint64_t max_paths = std::min<uint64_t>(Q.n, 1ull << log2);
+    Launch L{};
+    L.S = Q.S; L.P = Q.P; L.counters = Q.counters; L.count = Q.count; L.timer = Q.timer;
+    const uint32_t cap = depth_cap(L.P);
+    const DeviceLimits dev = device_limits();
+    const int tr = pick_trace(Q.trace_mode, L.S);
+    const bool march = has_marched(L.S);
+    const bool exact = march && L.S.n_msdf == 0u && MarchedC2Lds::matches(L.S.n_msph, L.S.n_mbox, L.S.n_mtor);
+    const bool l2_tree = tr_base(tr) == TR_BVH2_GLOBAL || tr_base(tr) == TR_BVH4_GLOBAL || tr_base(tr) == TR_BVH2_WIDE;
+    const uint32_t tail_at = Q.tail_bounce ? Q.tail_bounce : march ? std::max<uint32_t>(kTailMarched, 1u)
+                           : l2_tree ? kTailL2 : kTailDefault;
+    const uint32_t lanes_per_cu = (march || l2_tree) ? OM_WF_LANES_PER_CU_WIDE : OM_WF_LANES_PER_CU;
+    const uint32_t nseg = deal_segments(max_paths, (uint32_t)dev.cus, lanes_per_cu, kBlk, kTailSpb);
+    const uint32_t segcap = batch_deal(max_paths, nseg).capacity();
+    const uint32_t lds = trace_lds(tr, L.S);
+    const uint32_t tail_grid = (uint32_t)dev.cus * kTailWgsPerCu;
+    if (!march && tail_at < cap && tail_lds(lds, nseg) > (uint32_t)dev.lds_max) {
+        err = "the tail's LDS request exceeds the device's limit";
+        return hipErrorInvalidValue;
+    }
+    if (lds > (uint32_t)dev.lds_max) {
+        err = "the traversal's LDS request exceeds the device's limit";
+        return hipErrorInvalidValue;
+    }
+    // (an existing larger set, or more sets, stay as they are: grow never shrinks)
+    hipError_t e = grow(B, (uint64_t)nseg * segcap, count_rows(cap) * nseg + 1u, std::max(B.nsets, 1));
+    if (e != hipSuccess) { err = "wavefront buffer allocation failed"; return e; }
+    QueueSet& QS = B.set[0];
+    Timer& tm = *L.timer;
+    const int call_ti = tm.begin(st);
+    const Gen R{};
+    uint32_t launches = 0;
+    for (uint64_t at = 0; at < Q.n; at += max_paths) {
+        RaySrc X;
+        X.n = (uint32_t)std::min<uint64_t>(max_paths, Q.n - at);
+        X.rays = Q.rays + at;
+        X.rng = Q.rng ? Q.rng + at : nullptr;
+        X.stream0 = Q.stream_base + (uint32_t)at;                  // (mod 2^32)
+        X.sample = Q.sample;
+        Seg G;
+        G.nseg = nseg;
+        G.segcap = batch_deal(X.n, nseg).capacity();
+        with_tr(tr, [&](auto t) {
+            constexpr int TR = decltype(t)::value;
+            with_flags({L.count, march, exact && exact_view_built<TR>()}, [&](auto count, auto mar, auto ex) {
+                if constexpr (mar || !ex) launches += run_batch<TR, count, mar, ex>(QS, L, st, G, R, tail_at, lds, tail_grid, &X);
+            });
+        });
+        hipLaunchKernelGGL(k_radiance, dim3((X.n + 255u) / 256u), dim3(256), 0, st, (const float4*)QS.res,
+                           (const uint32_t*)QS.res_id, X.n, Q.out + at);
+        if ((e = hipGetLastError()) != hipSuccess) { err = "path query launch failed"; return e; }
     }
     tm.end(call_ti, OM_KT_BOUNCE_SPAN, st, launches);
     return hipSuccess;
