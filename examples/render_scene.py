@@ -9,6 +9,7 @@ the F12 save of main.rs:473-476.
     python examples/render_scene.py --width 1000 --height 666 --ao 16 0.5         # ambient occlusion, out/ao.bmp
     python examples/render_scene.py --mesh model.obj --spp 64                     # a triangle mesh over the ground
     python examples/render_scene.py --camera fisheye --spp 32                     # another camera model, out/fisheye.bmp
+    python examples/render_scene.py --camera pano --spp 64                        # a 360 degree frame with every view saved
 """
 import argparse
 import os
@@ -121,6 +122,49 @@ def render_camera_model(frozen, cam, W, H, model, spp, max_depth, seed):
     return np.ascontiguousarray(rgb.to(torch.uint8).reshape(H, W, 3).cpu().numpy())
 
 
+def frame_rays(model, cam, W, H, samples, rng):
+    """(samples, W*H, 6) float32 unit rays of a camera the renderer does not have, made on the host with
+    numpy in float32, sample-major as render_rays reads them, every sample with a sub-pixel jitter of
+    this example's own from `rng`:
+      ortho  parallel rays along the view direction through a 12-wide view rectangle centred on lookfrom;
+      pano   equirectangular, 360 x 180 degrees around lookfrom, the view direction in the middle."""
+    F = np.float32
+    r = cam.raw
+    org, cu, cv, cw = (np.array(list(v), dtype=F) for v in (r.origin, r.u_of_plane, r.v_of_plane, r.w_of_plane))
+    j, i = np.meshgrid(np.arange(H, dtype=F), np.arange(W, dtype=F), indexing="ij")
+    i, j = i.reshape(1, -1), j.reshape(1, -1)
+    jx, jy = rng.random((samples, W * H), dtype=F), rng.random((samples, W * H), dtype=F)
+    x = ((i + jx) / F(W) * F(2.0) - F(1.0)).astype(F)              # -1 .. 1 left to right
+    yv = (F(1.0) - (j + jy) / F(H) * F(2.0)).astype(F)             # 1 .. -1 top to bottom
+    if model == "ortho":
+        y = yv * F(H / W)
+        o = org + (F(6.0) * x)[..., None] * cu + (F(6.0) * y)[..., None] * cv
+        d = np.broadcast_to(-cw, o.shape)
+    else:
+        lon, lat = x * F(np.pi), yv * F(np.pi / 2.0)
+        d = (np.cos(lat) * np.sin(lon))[..., None] * cu + np.sin(lat)[..., None] * cv - (np.cos(lat) * np.cos(lon))[..., None] * cw
+        o = np.broadcast_to(org, d.shape)
+    d = d.astype(F)
+    d = (d / np.sqrt((d * d).sum(axis=2, dtype=F), dtype=F)[..., None]).astype(F)   # the unit-direction precondition
+    return np.ascontiguousarray(np.concatenate([o.astype(F), d], axis=2), dtype=F)
+
+
+def render_frame_camera(frozen, cam, W, H, model, args, pixels):
+    """The progressive loop of main() with the model's rays in the place of the thin lens: per call
+    `--per-call` samples through render_rays into the same Stats, adaptive retirement and credit as
+    render() has them, default RNG streams (seed, pixel, Stats.n).  Returns the credited samples."""
+    rng = np.random.default_rng(args.seed)
+    credited = 0
+    for done in range(0, args.spp, args.per_call):
+        rays = frame_rays(model, cam, W, H, min(args.per_call, args.spp - done), rng)
+        c = frozen.render_rays(pixels, rays, W, H, args.spp, max_depth=args.max_depth, adaptive=args.adaptive, seed=args.seed)
+        credited += c["credited"]
+        print(f"\r{100.0 * credited / (W * H * args.spp):5.1f}%", end="", flush=True)
+        if credited >= W * H * args.spp:                            # every pixel is full or retired
+            break
+    return credited
+
+
 def mesh_scene(path):
     """random_scene's ground sphere with the OBJ mesh standing on it: scaled to height 2, centred in x
     and z, one material, added with one add_triangles call."""
@@ -160,9 +204,11 @@ def main():
     ap.add_argument("--ao", nargs=2, metavar=("SAMPLES", "RADIUS"),
                     help="write ao.bmp/ppm: ambient occlusion from SAMPLES any-hit rays of length RADIUS per primary hit "
                          "(FrozenHittableList.occluded), and exit (no render)")
-    ap.add_argument("--camera", choices=("fisheye", "ortho", "equirect"),
-                    help="render through another camera model instead of the thin lens: its rays are built on the device "
-                         "with torch and traced with FrozenHittableList.ray_color, --spp calls of one sample each; writes "
+    ap.add_argument("--camera", choices=("thinlens", "ortho", "pano", "fisheye", "equirect"), default="thinlens",
+                    help="thinlens: the reference's camera through render().  ortho / pano: another camera's jittered rays, "
+                         "made with numpy, rendered progressively into the same Stats through FrozenHittableList.render_rays "
+                         "(adaptive retirement, every view saved).  fisheye / equirect: centre rays built on the device with "
+                         "torch and averaged from FrozenHittableList.ray_color, --spp calls of one sample each; writes "
                          "MODEL.bmp/ppm and exits")
     args = ap.parse_args()
 
@@ -195,7 +241,7 @@ def main():
         (om.write_ppm if args.ppm else om.write_bmp)(path, rgb)
         print("wrote", path)
         return
-    if args.camera:
+    if args.camera in ("fisheye", "equirect"):
         t0 = time.perf_counter()
         rgb = render_camera_model(frozen, cam, W, H, args.camera, args.spp, args.max_depth, args.seed)
         dt = time.perf_counter() - t0
@@ -207,13 +253,16 @@ def main():
         return
     pixels = om.PixelsBox.new(W * H)
     t0, credited = time.perf_counter(), 0
-    for done in range(0, args.spp, args.per_call):
-        c = om.render(cam, frozen, args.max_depth, 0.001, 100.0, args.spp, W, H, pixels, seed=args.seed,
-                      adaptive=args.adaptive, sample_count=min(args.per_call, args.spp - done))
-        credited += c["credited"]
-        print(f"\r{100.0 * credited / (W * H * args.spp):5.1f}%", end="", flush=True)   # main.rs:151-168 log
+    if args.camera != "thinlens":
+        credited = render_frame_camera(frozen, cam, W, H, args.camera, args, pixels)
+    else:
+        for done in range(0, args.spp, args.per_call):
+            c = om.render(cam, frozen, args.max_depth, 0.001, 100.0, args.spp, W, H, pixels, seed=args.seed,
+                          adaptive=args.adaptive, sample_count=min(args.per_call, args.spp - done))
+            credited += c["credited"]
+            print(f"\r{100.0 * credited / (W * H * args.spp):5.1f}%", end="", flush=True)   # main.rs:151-168 log
     dt = time.perf_counter() - t0
-    print(f"\n{W}x{H}x{args.spp} in {dt:.3f} s ({W * H * args.spp / dt / 1e6:.0f} Msamples/s credited)")
+    print(f"\n{W}x{H}x{args.spp} {args.camera} in {dt:.3f} s ({W * H * args.spp / dt / 1e6:.0f} Msamples/s credited)")
     os.makedirs(args.out, exist_ok=True)
     for view in L.VIEWS:
         rgb = om.display(frozen, pixels, W, H, view)

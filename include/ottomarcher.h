@@ -25,6 +25,7 @@
  *   om_upload_world       HittableList::freeze -> FrozenHittableList  hits.rs:87-89, 116-185
  *   om_hit_rays*   FrozenHittableList::hit   hits.rs:270-334
  *   om_ray_color*  ray_color                 render_thread.rs:128-143
+ *   om_render_rays*  render_thread::render's pass loop over caller-given rays   render_thread.rs:176-199
  *   om_render / om_render_device   render_thread::render (all threads of main.rs:200-214)
  *                                                                   render_thread.rs:145-202
  *   om_pixel_stats        Pixel/Stats                               render_thread.rs:9-51
@@ -411,6 +412,52 @@ om_status om_ray_color(om_ctx* ctx, const om_path_params* p, const om_ray* rays,
  * Larger calls run their batches one after another.  A pure scheduling knob: results are
  * bit-identical for every value. */
 om_status om_set_path_batch(om_ctx* ctx, uint32_t paths_log2);
+/* ---- frames from caller-given rays: any camera, the reference's Stats ----
+ * om_render with the caller's rays in the place of Camera::get_ray.  The table is sample-major:
+ * sample s (0 .. p->sample_count-1) of listed pixel k is rays[s * n_pixels + k] (a 64-bit index), and
+ * rng[s * n_pixels + k] likewise; the pixel of entry k is pixels[k], or k when pixels is NULL (then
+ * n_pixels must be width * height).  For s in order and every listed pixel the call applies the
+ * reference's rule: the sample is taken iff Stats.n < spp_total && !(adaptive && done).  A taken
+ * sample is ray_color(ray, world, max_depth, tmin, tmax) followed by Stats::add
+ * (render_thread.rs:23-39) as in om_render, with the credit of a retiring pixel's untaken samples and
+ * the om_progress word; one that is not taken reads no ray and traces nothing.  So a frame grows
+ * over any number of calls, and a pixel that is full or retired costs nothing in later ones.
+ *   rng      the path of a taken sample draws from rng[s * n_pixels + k] (an om_path_rng_state value)
+ *            or, with rng NULL, from the stream (p->seed, pixel, Stats.n at that sample) from its
+ *            start.  The jitter that made the rays is the caller's: there is no jitter table here,
+ *            spp_total only caps n and sizes the adaptive credit, and sample_begin is unused.
+ *   rays     om_ray with the unit-direction precondition of om_hit_rays*; bit-identity holds in the
+ *            domain of om_ray_color*, its reference loop for far origins included.  A ray with a NaN
+ *            or infinite component is not traced: its sample is the record colour (NaN, NaN, NaN),
+ *            depth +inf, obj 0, added to its pixel like any other, and it counts no segment.
+ *   pixels   row-major indices < width * height.  The host form checks them (OM_ERR_INVALID, nothing
+ *            written); for the device form the bound is a precondition, as for
+ *            om_render_device_pixels.  A list that names a pixel twice gives unspecified Stats for
+ *            that pixel, in both forms.
+ *   counters samples and credited are the reference's; segments, prim_tests, pre_tests and
+ *            march_steps are the work really traced: samples rendered inside a batch after their
+ *            pixel's retirement are dropped in sample order, as om_set_adaptive_batches documents,
+ *            and still count their segments.  om_set_counting applies as in renders.
+ * A sample_count, spp_total or n_pixels of 0 is OM_OK and launches nothing.  OM_ERR_INVALID: a null
+ * ctx or p; null rays or stats with work to do; width * height == 0; pixels NULL with n_pixels !=
+ * width * height; n_pixels > width * height; a NaN tmin / tmax; rng not 8-byte aligned (device
+ * form).  A call before om_upload_world is OM_ERR_STATE.  A failed call writes nothing.
+ * Like om_ray_color* the call always runs the wavefront's queues and tails (there is no megakernel
+ * form), with the ctx's kernel choice, om_set_tail_bounce and om_set_path_batch: a batch holds at
+ * most 2^paths_log2 paths, whole samples of the list first, ranges of a list longer than that;
+ * results do not depend on the cut.  om_set_pipeline and om_set_streams are ignored: the batches
+ * run one after another on the call's stream.  With om_set_timing on, the launches are timed in the
+ * render's classes, OM_KT_ACCUMULATE included. */
+/* Device form: the pointers are device memory on ctx's device; asynchronous on `stream` (NULL =
+ * ctx's own stream). */
+om_status om_render_rays_device(om_ctx* ctx, const om_render_params* p, const om_ray* dev_rays /* sample_count * n_pixels */,
+                                const uint64_t* dev_rng /* the same layout, or NULL */,
+                                const uint32_t* dev_pixels /* n_pixels indices, or NULL */, uint32_t n_pixels,
+                                om_pixel_stats* dev_stats /* width * height */, void* stream);
+/* Host form, synchronous: stages through ctx-owned buffers like om_ray_color, copies `stats` (the
+ * whole frame) both ways and resets / returns the counters like om_render. */
+om_status om_render_rays(om_ctx* ctx, const om_render_params* p, const om_ray* rays, const uint64_t* rng,
+                         const uint32_t* pixels, uint32_t n_pixels, om_pixel_stats* stats, om_counters* counters /* optional */);
 /* Page-lock a caller-owned host buffer (e.g. the framebuffer) so om_render's copies run as
  * DMA at full PCIe speed; the buffer must stay allocated until om_host_unregister. */
 om_status om_host_register(void* p, size_t bytes);

@@ -390,6 +390,22 @@ public:
         return out;
     }
     void set_path_batch(uint32_t paths_log2) { check(om_set_path_batch(ctx_, paths_log2), ctx_); }
+    // p.sample_count samples of a frame from caller-given rays (om_render_rays): ray_color of
+    // rays[s * n + k] added to the Stats of listed pixel k in sample order, by the renderer's rule
+    // (Stats.n < p.spp_total, adaptive retirement, credit).  `pixels` empty: the whole frame in
+    // row-major order, n = p.width * p.height.  The path draws from rng[s * n + k] or, with `rng`
+    // empty, from the stream (p.seed, pixel, Stats.n).  Returns the call's counters.
+    om_counters render_rays(std::vector<om_pixel_stats>& stats, const std::vector<om_ray>& rays, const om_render_params& p,
+                            const std::vector<uint64_t>& rng = {}, const std::vector<uint32_t>& pixels = {}) const {
+        const uint64_t frame = (uint64_t)p.width * p.height, n = pixels.empty() ? frame : pixels.size();
+        if (stats.size() != frame) throw Error(OM_ERR_INVALID, "render_rays: stats must hold width*height entries");
+        if (rays.size() != n * p.sample_count) throw Error(OM_ERR_INVALID, "render_rays: one ray per listed pixel and sample");
+        if (!rng.empty() && rng.size() != rays.size()) throw Error(OM_ERR_INVALID, "render_rays: one rng state per ray");
+        om_counters c{};
+        check(om_render_rays(ctx_, &p, rays.data(), rng.empty() ? nullptr : rng.data(), pixels.empty() ? nullptr : pixels.data(),
+                             (uint32_t)n, stats.data(), &c), ctx_);
+        return c;
+    }
 
 private:
     om_ctx* ctx_ = nullptr;

@@ -148,6 +148,7 @@ EXPORTS = [
     "om_occluded_rays_device", "om_occluded_rays", "om_hit_rays_windows_device", "om_hit_rays_windows",
     "om_world_add_triangles", "om_world_tree_info", "om_get_tree_info",
     "om_path_rng_state", "om_ray_color_device", "om_ray_color", "om_set_path_batch",
+    "om_render_rays_device", "om_render_rays",
 ]
 OM_COMM_ID_BYTES = 128
 OM_TRANSPORT_RCCL, OM_TRANSPORT_LOCAL = 0, 1
@@ -277,6 +278,8 @@ def _load():
         "om_ray_color_device": (st, [vp, C.POINTER(om_path_params), vp, vp, C.c_uint32, vp, vp]),
         "om_ray_color": (st, [vp, C.POINTER(om_path_params), vp, vp, C.c_uint32, vp]),
         "om_set_path_batch": (st, [vp, C.c_uint32]),
+        "om_render_rays_device": (st, [vp, C.POINTER(om_render_params), vp, vp, vp, C.c_uint32, vp, vp]),
+        "om_render_rays": (st, [vp, C.POINTER(om_render_params), vp, vp, vp, C.c_uint32, vp, C.POINTER(om_counters)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

@@ -607,6 +607,111 @@ class FrozenHittableList:
               self._ctx)
         return out
 
+    def render_rays(self, pixels_box, rays, image_width, image_height, samples_per_pixel, max_depth=50, tmin=0.001,
+                    tmax=100.0, march_steps=1024, rng=None, pixels=None, adaptive=True, seed=1, stream=None):
+        """Samples of a frame from caller-given rays: render()'s pass loop with `rays` in the place of
+        Camera::get_ray (om_render_rays / om_render_rays_device), for any camera model.
+
+        `rays` is (S, n, 6) or (S * n, 6) float32, sample-major: sample s of listed pixel k is row
+        s * n + k, and the call takes S samples.  The pixel of entry k is `pixels[k]` (row-major
+        indices, each at most once), or k with `pixels` None, where n = image_width * image_height.
+        For s in order, a pixel takes the sample iff its Stats.n < samples_per_pixel and, with
+        `adaptive`, it has not retired; the sample is ray_color(ray) added by Stats::add, as in
+        render().  A pixel that is full or retired reads no ray, so a frame can be grown over any
+        number of calls.  The path draws from `rng` (path_rng_state values, shaped like the rays
+        without the last axis) or, by default, from the stream (seed, pixel, Stats.n).
+
+        numpy in: `pixels_box` is a PixelsBox or a W*H array of om_pixel_stats, `rng` uint64, `pixels`
+        uint32; synchronous, returns the call's RenderStats.  torch ROCm tensors in: `pixels_box` is
+        the frame's Stats on the device, W*H records of 40 bytes in a contiguous tensor (for one a
+        (W*H, 40) uint8 tensor), `rng` int64, `pixels` int32 holding the uint32 indices; asynchronous
+        with the stream rules of hit_rays, returns None (counters() reads the counters)."""
+        what = "render_rays"
+        W, H = int(image_width), int(image_height)
+        if W <= 0 or H <= 0:
+            raise ValueError(f"{what}: image_width and image_height must be positive")
+        is_torch = lambda x: type(x).__module__.split(".")[0] == "torch"
+        given = [x for x in (rays, rng, pixels, pixels_box) if x is not None]
+        dev = is_torch(rays)
+        if any(is_torch(x) != dev for x in given):
+            raise ValueError(f"{what}: rays, rng, pixels and the Stats are all numpy or all torch")
+        if pixels is not None and (pixels.ndim != 1 or pixels.shape[0] > W * H):
+            raise ValueError(f"{what}: pixels is a vector of at most image_width * image_height indices")
+        n = W * H if pixels is None else int(pixels.shape[0])
+        if dev:
+            import torch
+            if not rays.is_cuda or rays.dtype != torch.float32 or not rays.is_contiguous():
+                raise ValueError(f"{what}: need contiguous float32 rays on the device")
+            if rays.device.index != int(self.device):
+                raise ValueError(f"{what}: rays are on {rays.device}, the world is on device {self.device}")
+        else:
+            rays = np.ascontiguousarray(rays)
+            if rays.dtype != np.float32:
+                raise ValueError(f"{what}: need float32 rays")
+        if rays.ndim == 3 and tuple(rays.shape[1:]) == (n, 6):
+            S = int(rays.shape[0])
+        elif rays.ndim == 2 and rays.shape[1] == 6 and n and rays.shape[0] % n == 0:
+            S = int(rays.shape[0]) // n
+        elif rays.ndim == 2 and rays.shape[1] == 6 and rays.shape[0] == 0:
+            S = 0
+        else:
+            raise ValueError(f"{what}: rays must be (S, {n}, 6) or (S * {n}, 6)")
+        p = make_params(max_depth, tmin, tmax, samples_per_pixel, W, H, sample_count=S, seed=seed,
+                        march_steps=march_steps, adaptive=adaptive)
+        if dev:
+            st = pixels_box
+            if not st.is_cuda or not st.is_contiguous() or st.device != rays.device \
+                    or st.numel() * st.element_size() != W * H * 40:
+                raise ValueError(f"{what}: the Stats must be a contiguous tensor of W*H 40-byte records on the rays' device")
+            if rng is not None and (not rng.is_cuda or rng.dtype != torch.int64 or rng.numel() != S * n
+                                    or not rng.is_contiguous() or rng.device != rays.device):
+                raise ValueError(f"{what}: rng must be a contiguous int64 tensor on the rays' device, one state per ray")
+            if pixels is not None and (not pixels.is_cuda or pixels.dtype != torch.int32 or not pixels.is_contiguous()
+                                       or pixels.device != rays.device):
+                raise ValueError(f"{what}: pixels must be a contiguous int32 tensor on the rays' device")
+            if stream is not None and int(stream) == 0:
+                raise ValueError(f"{what}: stream 0 is the ctx's own stream to the library; pass a stream or none")
+            cur = side = None
+            if stream is None:
+                cur = torch.cuda.current_stream(rays.device)
+                stream = cur.cuda_stream
+                if stream == 0:                                   # torch's null stream: order a side stream with it
+                    if getattr(self, "_torch_side", None) is None:
+                        self._torch_side = torch.cuda.Stream(device=rays.device)
+                    side = self._torch_side
+                    side.wait_stream(cur)
+                    stream = side.cuda_stream
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            try:
+                check(lib.om_render_rays_device(self._ctx, C.byref(p), ptr(rays), ptr(rng), ptr(pixels), n, ptr(st),
+                                                C.c_void_p(stream)), self._ctx)
+            finally:
+                if side is not None:
+                    for t in (rays, rng, pixels, st):
+                        if t is not None:
+                            t.record_stream(side)
+                    cur.wait_stream(side)
+            return None
+        buf = pixels_box.pixels if isinstance(pixels_box, PixelsBox) else pixels_box
+        if not isinstance(buf, np.ndarray) or buf.dtype != L.PIXEL_STATS_DTYPE or buf.size != W * H \
+                or not buf.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"{what}: pixels_box must be a contiguous W*H om_pixel_stats array")
+        rp = pp = None
+        if rng is not None:
+            if rng.dtype != np.uint64 or rng.size != S * n:
+                raise ValueError(f"{what}: rng must hold one uint64 state per ray")
+            rng = np.ascontiguousarray(rng)
+            rp = rng.ctypes.data_as(C.c_void_p)
+        if pixels is not None:
+            if pixels.dtype != np.uint32:
+                raise ValueError(f"{what}: pixels must be uint32")
+            pixels = np.ascontiguousarray(pixels)
+            pp = pixels.ctypes.data_as(C.c_void_p)
+        ctr = L.om_counters()
+        check(lib.om_render_rays(self._ctx, C.byref(p), rays.ctypes.data_as(C.c_void_p), rp, pp, n,
+                                 buf.ctypes.data_as(C.c_void_p), C.byref(ctr)), self._ctx)
+        return RenderStats({k: getattr(ctr, k) for k, _ in L.om_counters._fields_})
+
     def query_max_grid(self):
         """Workgroups of the largest query launch on this device (om_query_max_grid)."""
         return int(lib.om_query_max_grid(self._ctx))

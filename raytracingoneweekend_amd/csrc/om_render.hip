@@ -658,6 +658,95 @@ om_status om_set_path_batch(om_ctx* c, uint32_t paths_log2) {
     return OM_OK;
 }
 
+// ---- frames from caller-given rays ----
+// The checks both forms share; *work is false for a call that is OM_OK and launches nothing.
+static om_status validate_frame_rays(om_ctx* c, const om_render_params* p, const void* rays, const void* pixels, uint32_t n_pixels,
+                                     const void* stats, bool* work) {
+    *work = false;
+    if (!c) return set_err(nullptr, OM_ERR_INVALID, "om_render_rays: null ctx");
+    if (!p) return set_err(c, OM_ERR_INVALID, "om_render_rays: null params");
+    if (p->width == 0 || p->height == 0) return set_err(c, OM_ERR_INVALID, "width/height must be > 0");
+    const uint64_t frame = (uint64_t)p->width * p->height;
+    if (frame > (1ull << 31)) return set_err(c, OM_ERR_INVALID, "image too large");
+    if (!pixels && n_pixels != frame) return set_err(c, OM_ERR_INVALID, "om_render_rays: without a pixel list n_pixels is width * height");
+    if (n_pixels > frame) return set_err(c, OM_ERR_INVALID, "om_render_rays: more listed pixels than the frame has");
+    if (std::isnan(p->tmin) || std::isnan(p->tmax)) return set_err(c, OM_ERR_INVALID, "om_render_rays: tmin/tmax is NaN");
+    if (!c->have_world) return set_err(c, OM_ERR_STATE, "om_upload_world must precede rendering");
+    if (p->sample_count == 0 || p->spp_total == 0 || n_pixels == 0) return OM_OK;
+    if (!rays || !stats) return set_err(c, OM_ERR_INVALID, "om_render_rays: null rays/stats");
+    *work = true;
+    return OM_OK;
+}
+
+om_status om_render_rays_device(om_ctx* c, const om_render_params* p, const om_ray* dev_rays, const uint64_t* dev_rng,
+                                const uint32_t* dev_pixels, uint32_t n_pixels, om_pixel_stats* dev_stats, void* stream) {
+    bool work;
+    om_status s = validate_frame_rays(c, p, dev_rays, dev_pixels, n_pixels, dev_stats, &work);
+    if (s || !work) return s;
+    if (dev_rng && ((uintptr_t)dev_rng & 7u)) return set_err(c, OM_ERR_INVALID, "om_render_rays: rng must be 8-byte aligned");
+    OM_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    if (!c->counters.p) {
+        if ((s = ensure(c, c->counters, OMC_SLOTS * sizeof(unsigned long long))) != OM_OK) return s;
+        OM_HIP(c, hipMemsetAsync(c->counters.p, 0, OMC_SLOTS * sizeof(unsigned long long), st));
+    }
+    c->last_stream = st;
+    int mode = c->kernel;
+    if (mode == OM_KERNEL_AUTO) mode = OM_KERNEL_BVH2;
+    omw::FrameRays Q{};
+    Q.S = c->scene;
+    OmParamsDev& P = Q.P;
+    P.width = p->width; P.height = p->height; P.spp_total = p->spp_total; P.sample_count = p->sample_count;
+    P.max_depth = p->max_depth; P.march_steps = p->march_steps; P.adaptive = p->adaptive ? 1u : 0u;
+    P.tmin = p->tmin; P.tmax = p->tmax;
+    P.skey = host_mix64(p->seed + 0x632BE59BD9B4E019ULL);
+    P.progress = c->progress_host ? 1u : 0u;
+    P.n_pixels = n_pixels;
+    Q.rays = dev_rays; Q.rng = dev_rng; Q.pixels = dev_pixels; Q.n_pixels = n_pixels; Q.stats = dev_stats;
+    Q.counters = (unsigned long long*)c->counters.p;
+    Q.count = c->count_work;
+    Q.trace_mode = wf_trace_mode(mode);
+    Q.tail_bounce = c->tail_bounce;
+    Q.paths_log2 = c->path_batch_log2;
+    Q.timer = &c->timer;
+    Q.progress_host = c->progress_host;
+    std::string err;
+    const hipError_t e = omw::render_rays(c->wf, Q, st, err);
+    if (e != hipSuccess) return set_err(c, OM_ERR_DEVICE, err + ": " + hipGetErrorString(e));
+    return OM_OK;
+}
+
+om_status om_render_rays(om_ctx* c, const om_render_params* p, const om_ray* rays, const uint64_t* rng, const uint32_t* pixels,
+                         uint32_t n_pixels, om_pixel_stats* stats, om_counters* counters) {
+    bool work;
+    om_status s = validate_frame_rays(c, p, rays, pixels, n_pixels, stats, &work);
+    if (s) return s;
+    const uint32_t frame = p->width * p->height;
+    if (work && pixels)
+        for (uint32_t k = 0; k < n_pixels; ++k)
+            if (pixels[k] >= frame) return set_err(c, OM_ERR_INVALID, "om_render_rays: a listed pixel is outside the frame");
+    OM_HIP(c, hipSetDevice(c->device));
+    if ((s = om_reset_counters(c, c->stream)) != OM_OK) return s;
+    if (work) {
+        const size_t n = (size_t)p->sample_count * n_pixels, bytes = (size_t)frame * sizeof(om_pixel_stats);
+        if ((s = ensure(c, c->query_rays, n * sizeof(om_ray))) != OM_OK) return s;
+        if (rng && (s = ensure(c, c->path_rng, n * sizeof(uint64_t))) != OM_OK) return s;
+        if (pixels && (s = ensure(c, c->pixels, (size_t)n_pixels * sizeof(uint32_t))) != OM_OK) return s;
+        if ((s = ensure(c, c->stats, bytes)) != OM_OK) return s;
+        OM_HIP(c, hipMemcpyAsync(c->query_rays.p, rays, n * sizeof(om_ray), hipMemcpyHostToDevice, c->stream));
+        if (rng) OM_HIP(c, hipMemcpyAsync(c->path_rng.p, rng, n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        if (pixels) OM_HIP(c, hipMemcpyAsync(c->pixels.p, pixels, (size_t)n_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        OM_HIP(c, hipMemcpyAsync(c->stats.p, stats, bytes, hipMemcpyHostToDevice, c->stream));
+        s = om_render_rays_device(c, p, (const om_ray*)c->query_rays.p, rng ? (const uint64_t*)c->path_rng.p : nullptr,
+                                  pixels ? (const uint32_t*)c->pixels.p : nullptr, n_pixels, (om_pixel_stats*)c->stats.p, c->stream);
+        if (s != OM_OK) return s;
+        OM_HIP(c, hipMemcpyAsync(stats, c->stats.p, bytes, hipMemcpyDeviceToHost, c->stream));
+        OM_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    if (counters) return om_get_counters(c, counters);
+    return OM_OK;
+}
+
 uint32_t om_query_max_grid(om_ctx* c) {
     if (!c) { set_err(nullptr, OM_ERR_INVALID, "om_query_max_grid: null ctx"); return 0u; }
     if (hipSetDevice(c->device) != hipSuccess) { set_err(c, OM_ERR_DEVICE, "om_query_max_grid: hipSetDevice"); return 0u; }

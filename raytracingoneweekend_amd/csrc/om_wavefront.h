@@ -131,6 +131,27 @@ struct PathQuery {
 // Queues the batches of Q on `stream`, through queue set 0 of B.
 hipError_t ray_color(Buffers& B, const PathQuery& Q, hipStream_t stream, std::string& err);
 
+// One frame call from caller-given rays (om_render_rays*_device): P.sample_count samples
+// of the listed pixels, ray_color of rays[s * n_pixels + k] added to stats[pixel of k] in sample order.
+struct FrameRays {
+    OmSceneDev S;
+    OmParamsDev P;               // as a render's; the camera-only fields (wf_m1, hf_m1, tiles_x) unused
+    const om_ray* rays;          // device, sample_count * n_pixels records, sample-major
+    const uint64_t* rng;         // device, the same layout; null: (skey, pixel, Stats.n at the sample)
+    const uint32_t* pixels;      // device, n_pixels row-major pixel indices; null: the whole frame in order
+    uint32_t n_pixels;
+    om_pixel_stats* stats;       // device, the frame, by pixel
+    unsigned long long* counters;
+    bool count;
+    int trace_mode;              // as Launch::trace_mode
+    uint32_t tail_bounce;        // as Launch::tail_bounce
+    uint32_t paths_log2;         // as PathQuery::paths_log2
+    Timer* timer;
+    unsigned long long* progress_host;   // as Launch::progress_host
+};
+// Queues the batches of Q on `stream`, through queue set 0 of B.
+hipError_t render_rays(Buffers& B, const FrameRays& Q, hipStream_t stream, std::string& err);
+
 // One batch of ray queries: closest-hit (om_hit_rays*_device) when `occluded` is
 // null, any-hit (om_occluded_rays_device, §5.16) otherwise.
 struct Query {

@@ -213,6 +213,18 @@ struct RaySrc {
     uint32_t stream0, sample;
 };
 
+// Path source of a render_rays batch (k_frame_paths): a rectangle of the call's sample-major ray
+// table, `range` listed pixels from the batch's first one times `samples` samples from its first.
+struct FrameSrc {
+    const om_ray* rays;          // the ray of the batch's first pixel and sample; sample rows ray_stride apart
+    const uint64_t* rng;         // PathRng states, the same layout; null: path_rng(skey, pixel, Stats.n + s_local)
+    uint64_t ray_stride;         // listed pixels of the call
+    const om_pixel_stats* stats; // the frame, by pixel
+    const uint32_t* pixels;      // the batch's first list entry; null: pixel = pixel0 + kk
+    uint32_t pixel0;
+    uint32_t range, samples;     // range * samples paths; range is the result slots' sample stride
+};
+
 // A path between bounces: ray_color's loop state (render_thread.rs:128-143).
 struct Path {
     F3 o, d, cur;
@@ -1251,6 +1263,107 @@ __global__ __launch_bounds__(256) void k_radiance(const float4* __restrict__ res
     __builtin_nontemporal_store(__uint_as_float(id), o + 4);
 }
 
+// k_frame_paths: k_paths for a frame (om_render_rays*).  The batch is the rectangle F
+// of the caller's sample-major ray table; path i of it is sample s_local = i / F.range of listed
+// pixel kk = i % F.range, its result slot is i, which is where k_accumulate's fixed-list form reads
+// sample s_local of list entry kk, and its ray is F.rays[s_local * F.ray_stride + kk].  A sample is
+// taken by gen_path's serial rule on the live Stats (the previous batch's k_accumulate ran on this
+// stream): Stats.n + s_local < spp_total and, in adaptive calls, not done.  One that is not taken
+// stores kNoSample and loads neither ray nor state.  With F.rng null the path draws from
+// path_rng(P.skey, pixel, Stats.n + s_local).  Staging, far origins, non-finite rays, the march of
+// segment 0, compaction and counters are k_paths's.
+template <int TR, bool COUNT, bool MARCH, bool USER>
+__global__ __launch_bounds__(kBlk) OM_WAVES_ATTR void k_frame_paths(OmSceneDev S, OmParamsDev P, Seg G, FrameSrc F, Queue out,
+                                                      uint32_t* __restrict__ count_out, float4* __restrict__ res,
+                                                      uint32_t* __restrict__ res_id, unsigned long long* __restrict__ counters,
+                                                      uint32_t* __restrict__ tail_next) {
+    if (tail_next && blockIdx.x == 0 && threadIdx.x == 0) *tail_next = 0u;
+    const uint64_t seg0 = (uint64_t)blockIdx.x * G.segcap;
+    const uint32_t n = F.range * F.samples;                          // (at most 2^OM_WF_MAX_PATHS_LOG2)
+    const Deal dl = batch_deal(n, G.nseg);
+    const uint32_t chunks = dl.blocks_of(blockIdx.x);
+    if (chunks == 0) {
+        if (threadIdx.x == 0) count_out[blockIdx.x] = 0u;
+        return;
+    }
+    __shared__ uint32_t q_next, q_out;
+    if (threadIdx.x == 0) { q_next = kBlk / 64u; q_out = 0u; }
+    __syncthreads();
+    const Tracer T = stage_scene<TR>(S);
+    const uint32_t cap = depth_cap(P);
+    WorkT<COUNT, false, tr_bary(TR)> w;
+    uint32_t segs = 0;
+    const uint32_t lane = __lane_id();
+    for (uint32_t chunk = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); chunk < chunks;) {   // wave-uniform
+        const uint32_t i = (uint32_t)(dl.block(blockIdx.x, chunk) * 64u) + lane;
+        bool keep = false;
+        Path p;
+        bool live = i < n;
+        uint64_t at = 0;
+        uint32_t pixel = 0, s = 0;
+        if (live) {
+            const uint32_t s_local = i / F.range, kk = i - s_local * F.range;
+            pixel = F.pixels ? F.pixels[kk] : F.pixel0 + kk;
+            const om_pixel_stats& ps = F.stats[pixel];
+            s = ps.n + s_local;
+            at = (uint64_t)s_local * F.ray_stride + kk;
+            if (!(s < P.spp_total && !(P.adaptive && (ps.flags & 1u)))) {
+                res_id[i] = kNoSample;
+                live = false;
+            }
+        }
+        if (live) {
+            load_query_ray(F.rays, at, p.o, p.d);
+            if (!(p.o.x * 0.0f + p.o.y * 0.0f + p.o.z * 0.0f + p.d.x * 0.0f + p.d.y * 0.0f + p.d.z * 0.0f == 0.0f)) {   // not traced (k_paths)
+                const float qnan = __uint_as_float(0x7FC00000u);
+                res[i] = make_float4(qnan, qnan, qnan, INFINITY);
+                res_id[i] = 0u;
+                live = false;
+            }
+        }
+        if (live) {
+            if (F.rng) {
+                const uint32_t* st = (const uint32_t*)(F.rng + at);
+                p.g.s = __builtin_nontemporal_load(st); p.g.k = __builtin_nontemporal_load(st + 1);
+            } else {
+                p.g = path_rng(P.skey, pixel, s);
+            }
+            p.cur = f3(1.0f, 1.0f, 1.0f); p.depthf = 0.0f; p.first_id = 0u; p.seg = 0u; p.slot = i;
+            float closest = P.tmax;
+            int best;
+            if (far_origin(S, p.o))
+                best = traced_brute<false>(S, p.o, p.d, P.tmin, closest, w);
+            else
+                best = trace_traced<TR>(S, T, p.o, p.d, P.tmin, closest, w);
+            if (MARCH) {
+                float tm;
+                const int mg = march(S, p.o, p.d, P.tmin, P.tmax, closest, P.march_steps, tm, w);
+                if (mg >= 0) { best = mg; closest = tm; }
+            }
+            keep = shade_path<MARCH, USER>(S, P, cap, p, closest, best, res, res_id);
+            if (COUNT) segs++;
+        }
+        const uint64_t m = __ballot(keep);
+        uint32_t obase = 0u, nc = 0u;
+        if (lane == 0) {
+            obase = m ? atomicAdd(&q_out, (uint32_t)__popcll(m)) : 0u;
+            nc = atomicAdd(&q_next, 1u);
+        }
+        obase = __builtin_amdgcn_readfirstlane(obase);
+        chunk = __builtin_amdgcn_readfirstlane(nc);
+        const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (keep) store_path(out, seg0 + obase + rank, p);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) count_out[blockIdx.x] = q_out;
+    if (COUNT) {
+        flush_counter(counters, OMC_SEGMENTS, segs);
+        flush_counter(counters, OMC_PRIM_TESTS, w.prim);
+        flush_counter(counters, OMC_PRE_TESTS, w.pre);
+        flush_counter(counters, OMC_MARCH, w.march);
+    }
+}
+
 // ---------------------------------------------------------------- accumulate
 // Adaptive batches (ad.list): lane kk owns live-list entry kk, and a pixel that is still live after
 // the batch, with samples of the call left, is appended to the stream's next list (one ballot and
@@ -1436,9 +1549,11 @@ inline uint32_t count_rows(uint32_t depth_cap) { return std::max<uint32_t>(depth
 // X (ray_color batches): segment 0 is k_paths over the caller's rays instead of the camera's launch
 // (k_raygen and bounce 0's k_march pair, or k_bounce<FIRST> with its fused bounce 1); its out queue
 // is bounce 1's, and everything from there on is the render's.  R is then unused by the kernels.
+// F (render_rays batches): the same with k_frame_paths over the batch's rectangle of the frame's rays.
 template <int TR, bool COUNT, bool MARCH, bool EXACT>
 uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Gen& R, uint32_t tail_at, uint32_t lds,
-                   uint32_t tail_grid, const RaySrc* X = nullptr) {
+                   uint32_t tail_grid, const RaySrc* X = nullptr, const FrameSrc* F = nullptr) {
+    const bool ext = X || F;                                     // segment 0 from the caller's rays
     constexpr int VIEW = EXACT && exact_view_built<TR>() ? MV_EXACT_C2_LDS : MV_ARRAYS;
     Timer& tm = *L.timer;
     const bool each = tm.mode == 1;
@@ -1465,7 +1580,10 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
         // buffer and k_bounce<HIT> shades and compacts
         {
             const int ti = each ? tm.begin(st) : -1;
-            if (X)
+            if (F)
+                hipLaunchKernelGGL((k_frame_paths<TR, COUNT, true, !EXACT>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, *F, queue(B, 1),
+                                   B.counts + G.nseg, B.res, B.res_id, L.counters, (uint32_t*)nullptr);
+            else if (X)
                 hipLaunchKernelGGL((k_paths<TR, COUNT, true, !EXACT>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, *X, queue(B, 1),
                                    B.counts + G.nseg, B.res, B.res_id, L.counters, (uint32_t*)nullptr);
             else
@@ -1473,7 +1591,7 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
             tm.end(ti, OM_KT_BOUNCE0, st);
             ++launches;
         }
-        for (uint32_t bounce = X ? 1u : 0u; bounce < cap; ++bounce) {
+        for (uint32_t bounce = ext ? 1u : 0u; bounce < cap; ++bounce) {
             const Queue in = queue(B, bounce & 1u), out = queue(B, (bounce + 1u) & 1u);
             const uint32_t* cin = B.counts + (size_t)bounce * G.nseg;
             if (bounce >= tail_at) return tail(in, cin);   // (tail_at 0: k_raygen's camera paths too)
@@ -1494,13 +1612,16 @@ uint32_t run_batch(QueueSet& B, const Launch& L, hipStream_t st, Seg G, const Ge
     // (fused first launch: bounces 0 and 1, its out queue is bounce 2's; the first queue the tail or a
     // per-bounce launch can read is the one that launch wrote, whatever tail_at asks for)
     for (uint32_t bounce = 0, next; bounce < cap; bounce = next) {
-        next = bounce + (bounce == 0 && kFuseB1 && !X ? 2u : 1u);
+        next = bounce + (bounce == 0 && kFuseB1 && !ext ? 2u : 1u);
         const Queue in = queue(B, bounce & 1u), out = queue(B, next & 1u);
         const uint32_t* cin = B.counts + (size_t)bounce * G.nseg;
         if (bounce > 0 && bounce >= tail_at) return tail(in, cin);
         uint32_t* cout = B.counts + (size_t)next * G.nseg;
         const int ti = each ? tm.begin(st) : -1;
-        if (bounce == 0 && X)
+        if (bounce == 0 && F)
+            hipLaunchKernelGGL((k_frame_paths<TR, COUNT, false, false>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, *F, out, cout,
+                               B.res, B.res_id, L.counters, tail_next);
+        else if (bounce == 0 && X)
             hipLaunchKernelGGL((k_paths<TR, COUNT, false, false>), dim3(G.nseg), dim3(kBlk), lds, st, L.S, L.P, G, *X, out, cout,
                                B.res, B.res_id, L.counters, tail_next);
         else if (bounce == 0)
@@ -1852,6 +1973,95 @@ hipError_t ray_color(Buffers& B, const PathQuery& Q, hipStream_t st, std::string
         hipLaunchKernelGGL(k_radiance, dim3((X.n + 255u) / 256u), dim3(256), 0, st, (const float4*)QS.res,
                            (const uint32_t*)QS.res_id, X.n, Q.out + at);
         if ((e = hipGetLastError()) != hipSuccess) { err = "path query launch failed"; return e; }
+    }
+    tm.end(call_ti, OM_KT_BOUNCE_SPAN, st, launches);
+    return hipSuccess;
+}
+
+// A frame from the caller's rays (om_render_rays*): Q.P.sample_count samples of the
+// Q.n_pixels listed pixels, ray_color of Q.rays[s * n_pixels + k] added to the pixel's Stats in
+// sample order.  A batch is a rectangle of the call with at most 2^paths_log2 paths: all listed
+// pixels times as many whole samples as fit, or, for a list longer than a batch, a range of the list
+// times one sample.  Per pixel range the sample batches run in order, one after another on `st`
+// through queue set 0: k_frame_paths (liveness on the live Stats, segment 0), run_batch's launches and
+// tail, k_accumulate in its fixed-list form over the range.  The previous batch's accumulate has run
+// when k_frame_paths reads the Stats, so a full or retired pixel costs a kNoSample store per sample
+// from the next batch on; inside a batch its later samples are traced and dropped in sample order.
+hipError_t render_rays(Buffers& B, const FrameRays& Q, hipStream_t st, std::string& err) {
+    const uint32_t n_px = Q.n_pixels, S_call = Q.P.sample_count;
+    if (n_px == 0 || S_call == 0 || Q.P.spp_total == 0) return hipSuccess;
+    const uint32_t log2 = Q.paths_log2 ? Q.paths_log2 : (uint32_t)OM_WF_QUERY_PATHS_LOG2;
+    const uint64_t batch_paths = 1ull << log2;
+    const uint32_t range_max = (uint32_t)std::min<uint64_t>(n_px, batch_paths);
+    const uint32_t b_max = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(S_call, batch_paths / range_max));
+    const uint64_t max_paths = (uint64_t)range_max * b_max;
+    Launch L{};
+    L.S = Q.S; L.P = Q.P; L.counters = Q.counters; L.count = Q.count; L.timer = Q.timer;
+    const uint32_t cap = depth_cap(L.P);
+    const DeviceLimits dev = device_limits();
+    const int tr = pick_trace(Q.trace_mode, L.S);
+    const bool march = has_marched(L.S);
+    const bool exact = march && L.S.n_msdf == 0u && MarchedC2Lds::matches(L.S.n_msph, L.S.n_mbox, L.S.n_mtor);
+    const bool l2_tree = tr_base(tr) == TR_BVH2_GLOBAL || tr_base(tr) == TR_BVH4_GLOBAL || tr_base(tr) == TR_BVH2_WIDE;
+    // (ray_color's threshold: there is no fused first launch here either)
+    const uint32_t tail_at = Q.tail_bounce ? Q.tail_bounce : march ? std::max<uint32_t>(kTailMarched, 1u)
+                           : l2_tree ? kTailL2 : kTailDefault;
+    const uint32_t lanes_per_cu = (march || l2_tree) ? OM_WF_LANES_PER_CU_WIDE : OM_WF_LANES_PER_CU;
+    const uint32_t nseg = deal_segments(max_paths, (uint32_t)dev.cus, lanes_per_cu, kBlk, kTailSpb);
+    const uint32_t segcap = batch_deal(max_paths, nseg).capacity();
+    const uint32_t lds = trace_lds(tr, L.S);
+    const uint32_t tail_grid = (uint32_t)dev.cus * kTailWgsPerCu;
+    if (!march && tail_at < cap && tail_lds(lds, nseg) > (uint32_t)dev.lds_max) {
+        err = "the tail's LDS request exceeds the device's limit";
+        return hipErrorInvalidValue;
+    }
+    if (lds > (uint32_t)dev.lds_max) {
+        err = "the traversal's LDS request exceeds the device's limit";
+        return hipErrorInvalidValue;
+    }
+    hipError_t e = grow(B, (uint64_t)nseg * segcap, count_rows(cap) * nseg + 1u, std::max(B.nsets, 1));
+    if (e != hipSuccess) { err = "wavefront buffer allocation failed"; return e; }
+    QueueSet& QS = B.set[0];
+    Timer& tm = *L.timer;
+    const int call_ti = tm.begin(st);
+    const Gen R{};
+    uint32_t launches = 0;
+    for (uint32_t k0 = 0; k0 < n_px; k0 += range_max) {
+        const uint32_t range = std::min(range_max, n_px - k0);
+        for (uint32_t s0 = 0; s0 < S_call; s0 += b_max) {
+            const uint32_t b = std::min(b_max, S_call - s0);
+            const uint64_t first = (uint64_t)s0 * n_px + k0;
+            FrameSrc F;
+            F.rays = Q.rays + first;
+            F.rng = Q.rng ? Q.rng + first : nullptr;
+            F.ray_stride = n_px;
+            F.stats = Q.stats;
+            F.pixels = Q.pixels ? Q.pixels + k0 : nullptr;
+            F.pixel0 = k0;
+            F.range = range; F.samples = b;
+            Seg G;
+            G.nseg = nseg;
+            G.segcap = batch_deal((uint64_t)range * b, nseg).capacity();
+            with_tr(tr, [&](auto t) {
+                constexpr int TR = decltype(t)::value;
+                with_flags({L.count, march, exact && exact_view_built<TR>()}, [&](auto count, auto mar, auto ex) {
+                    if constexpr (mar || !ex)
+                        launches += run_batch<TR, count, mar, ex>(QS, L, st, G, R, tail_at, lds, tail_grid, nullptr, &F);
+                });
+            });
+            // list entry kk of the range: pixels[k0 + kk], or pixel k0 + kk of a whole frame
+            const int ati = tm.mode == 1 ? tm.begin(st) : -1;
+            with_flags({L.count}, [&](auto count) {
+                hipLaunchKernelGGL(k_accumulate<count>, dim3((range + kBlk - 1u) / kBlk), dim3(kBlk), 0, st, L.P,
+                                   Q.pixels ? Q.stats : Q.stats + k0, F.pixels, range, Q.pixels ? 1u : 0u, b,
+                                   (const float4*)QS.res, (const uint32_t*)QS.res_id, L.S.bloom, AdList{}, L.counters);
+            });
+            tm.end(ati, OM_KT_ACCUMULATE, st);
+            if (Q.progress_host)
+                (void)hipMemcpyAsync(Q.progress_host, L.counters + OMC_PROGRESS, sizeof(unsigned long long),
+                                     hipMemcpyDeviceToHost, st);
+            if ((e = hipGetLastError()) != hipSuccess) { err = "render_rays launch failed"; return e; }
+        }
     }
     tm.end(call_ti, OM_KT_BOUNCE_SPAN, st, launches);
     return hipSuccess;
