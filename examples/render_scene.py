@@ -10,6 +10,7 @@ the F12 save of main.rs:473-476.
     python examples/render_scene.py --mesh model.obj --spp 64                     # a triangle mesh over the ground
     python examples/render_scene.py --camera fisheye --spp 32                     # another camera model, out/fisheye.bmp
     python examples/render_scene.py --camera pano --spp 64                        # a 360 degree frame with every view saved
+    python examples/render_scene.py --wave 8 --spp 32                             # a moving heightfield, refitted in place per frame
 """
 import argparse
 import os
@@ -182,6 +183,39 @@ def mesh_scene(path):
     return world
 
 
+def wave_field(phase, cells=96):
+    """a heightfield over [-4, 4]^2 whose sine's phase is `phase`"""
+    f32 = np.float32
+    fn = lambda x, z: (f32(0.35) * np.sin(f32(1.6) * x.astype(f32) + f32(phase), dtype=f32) * np.cos(f32(1.2) * z.astype(f32), dtype=f32)
+                       + f32(0.45)).astype(f32)
+    return om.heightfield(cells, cells, fn, extent=((-4.0, 4.0), (-4.0, 4.0)))
+
+
+def render_wave(args, W, H):
+    """--wave FRAMES: a short sequence of a heightfield whose phase advances per frame.  The world is
+    frozen once; every later frame moves the mesh in place with FrozenHittableList.update_triangles
+    (no re-upload, no rebuild) and renders it."""
+    v, f = wave_field(0.0)
+    world = om.HittableList.new()
+    world += om.Sphere.new_with_radius((0.0, -1000.0, 0.0), 1000.0, om.Material.new_lambertian((0.5, 0.5, 0.5)))
+    world += om.Sphere.new_with_radius((0.0, 1.6, 0.0), 0.7, om.Material.new_metal((0.8, 0.8, 0.9)))
+    world.add_triangles(v, f, om.Material.new_lambertian((0.2, 0.5, 0.8)))
+    cam = om.Camera.new((7.0, 4.5, 8.0), (0.0, 0.4, 0.0), (0.0, 1.0, 0.0), 35.0, W / H, 0.05, 11.0)
+    frozen = world.freeze(cam)
+    os.makedirs(args.out, exist_ok=True)
+    for k in range(args.wave):
+        t0 = time.perf_counter()
+        if k:
+            frozen.update_triangles(wave_field(0.35 * k)[0], f)
+        t1 = time.perf_counter()
+        pixels = om.PixelsBox.new(W * H)
+        om.render(cam, frozen, args.max_depth, 0.001, 100.0, args.spp, W, H, pixels, seed=args.seed, adaptive=args.adaptive)
+        path = os.path.join(args.out, f"wave_{k:03d}.{'ppm' if args.ppm else 'bmp'}")
+        (om.write_ppm if args.ppm else om.write_bmp)(path, om.display(frozen, pixels, W, H, "normal"))
+        print(f"frame {k}: update {1e3 * (t1 - t0):.2f} ms (host form, copies included), render {time.perf_counter() - t1:.3f} s, wrote {path}")
+    print("updates:", frozen.update_info())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1000)           # main.rs:125-127
@@ -210,9 +244,15 @@ def main():
                          "(adaptive retirement, every view saved).  fisheye / equirect: centre rays built on the device with "
                          "torch and averaged from FrozenHittableList.ray_color, --spp calls of one sample each; writes "
                          "MODEL.bmp/ppm and exits")
+    ap.add_argument("--wave", type=int, metavar="FRAMES",
+                    help="render FRAMES frames of a heightfield whose phase advances per frame, moved in place between "
+                         "frames with FrozenHittableList.update_triangles (wave_000.bmp ...), and exit")
     args = ap.parse_args()
 
     W, H = args.width, args.height
+    if args.wave:
+        render_wave(args, W, H)
+        return
     if args.mesh:
         world = mesh_scene(args.mesh)
         cam = om.Camera.new((5.0, 2.5, 6.0), (0.0, 1.0, 0.0), (0.0, 1.0, 0.0), 30.0, W / H, 0.05, 8.0)

@@ -201,6 +201,13 @@ om_status om_world_add_triangle(om_world* w, const float origin[3], const float 
  * BVH trees beside the spheres and cubes: rays cost O(log n) in the mesh size, with the same answers. */
 om_status om_world_add_triangles(om_world* w, const float* vertices /* 3*n_vertices */, uint32_t n_vertices,
                                  const uint32_t* indices /* 3*n_tri */, uint32_t n_tri, const om_material* m);
+/* Move triangles of the host world: triangles [first_triangle, first_triangle + n_tri) of the triangle
+ * kind (the order they were added in, by om_world_add_triangle and om_world_add_triangles alike) become
+ * Barycentric::new3points(v[i[3k]], v[i[3k+1]], v[i[3k+2]]); materials and obj ids stay.  indices NULL:
+ * triangle k uses vertices 3k, 3k+1, 3k+2.  All or nothing, validated like om_world_add_triangles; a
+ * range past the world's triangles is OM_ERR_INVALID, n_tri == 0 is OM_OK. */
+om_status om_world_update_triangles(om_world* w, uint32_t first_triangle, const float* vertices /* 3*n_vertices */, uint32_t n_vertices,
+                                    const uint32_t* indices /* 3*n_tri or NULL */, uint32_t n_tri);
 om_status om_world_add_parallelogram(om_world* w, const float origin[3], const float upoint[3], const float vpoint[3], const om_material* m);
 om_status om_world_add_triangle_basis(om_world* w, const float origin[3], const float u[3], const float v[3], float u_length, float v_length, const om_material* m);
 om_status om_world_add_parallelogram_basis(om_world* w, const float origin[3], const float u[3], const float v[3], float u_length, float v_length, const om_material* m);
@@ -272,6 +279,29 @@ om_status om_set_kernel(om_ctx* ctx, int32_t kernel);
  * ctx's kernel choice (OM_TREE_NONE for a choice that walks no BVH2: brute, culled, bvh, sbvh, or a
  * BVH4 that exists).  OM_ERR_STATE before om_upload_world. */
 om_status om_get_tree_info(om_ctx* ctx, om_tree_info* out);
+/* Move triangles of the uploaded world in place: the change of om_world_update_triangles
+ * applied to ctx's device copy without a freeze.  The records are rewritten and every tree is refitted:
+ * the topology of the upload stays, every box is recomputed bottom-up, so every answer stays the
+ * reference loop's, bit for bit, for the moved geometry (a mesh that moves far from its uploaded shape
+ * is traced more slowly; om_upload_world rebuilds).  om_get_tree_info is unchanged by an update.
+ * Device form: device pointers, asynchronous on `stream` (NULL = ctx's stream), ordered on it like a
+ * render: calls queued before it see the old mesh, calls after it the new one (one ctx is driven from
+ * one stream at a time).  The indices cannot be checked on the host: a triangle with an index
+ * >= n_vertices is left as it was and counted in om_update_info::skipped; nothing outside
+ * dev_vertices[0, 3*n_vertices) is read.  Host form: synchronous, staged through ctx; an index
+ * >= n_vertices is OM_ERR_INVALID.  n_tri == 0 is OM_OK and launches nothing; a range past the
+ * world's triangles or null vertices with work to do is OM_ERR_INVALID; OM_ERR_STATE before
+ * om_upload_world.  A failed call writes nothing. */
+om_status om_update_triangles_device(om_ctx* ctx, uint32_t first_triangle, const float* dev_vertices, uint32_t n_vertices,
+                                     const uint32_t* dev_indices, uint32_t n_tri, void* stream);
+om_status om_update_triangles(om_ctx* ctx, uint32_t first_triangle, const float* vertices, uint32_t n_vertices,
+                              const uint32_t* indices, uint32_t n_tri);
+/* updates: calls with work since the upload; of the last one: triangles rewritten, those whose new
+ * record or box holds a non-finite value (they get an all-covering box: every ray runs their exact
+ * test), and those skipped for an index outside the vertices (device form) */
+typedef struct om_update_info { uint32_t updates, triangles, unbounded, skipped; } om_update_info;  /* 16 B */
+/* synchronises like om_get_counters */
+om_status om_get_update_info(om_ctx* ctx, om_update_info* out);
 /* Host framebuffer path: `stats` is caller-owned W*H, read and written in place
  * (like PixelsBox, main.rs:192).  Includes the PCIe copies: 40 B per pixel each way per
  * call, at DMA speed when the buffer is page-locked (om_host_register), else staged by the

@@ -248,6 +248,13 @@ public:
         check(om_world_add_triangles(w_, vertices, n_vertices, indices, n_tri, &material.raw));
         return *this;
     }
+    // Move triangles [first, first + n_tri) of the triangle kind to new vertices (om_world_update_triangles;
+    // indices null: triangle k takes vertices 3k, 3k + 1, 3k + 2).  Materials and obj ids stay; all or nothing.
+    HittableList& update_triangles(const float* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_tri,
+                                   uint32_t first = 0) {
+        check(om_world_update_triangles(w_, first, vertices, n_vertices, indices, n_tri));
+        return *this;
+    }
     HittableList& operator+=(const Parallelogram& p) {
         check(p.three_points ? om_world_add_parallelogram(w_, p.origin.data(), p.u.data(), p.v.data(), &p.material.raw)
                              : om_world_add_parallelogram_basis(w_, p.origin.data(), p.u.data(), p.v.data(), p.u_length,
@@ -328,6 +335,20 @@ public:
     }
     void set_pipeline(int32_t pipeline) { check(om_set_pipeline(ctx_, pipeline), ctx_); }
     om_ctx* ctx() const { return ctx_; }
+
+    // Move triangles of the uploaded world in place, without a freeze (om_update_triangles, host form:
+    // synchronous): the records are rewritten and every tree is refitted, so every
+    // later answer is the reference's for the moved mesh.  An index past the vertices throws and
+    // changes nothing.  The device form is om_update_triangles_device on ctx().
+    void update_triangles(const float* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_tri, uint32_t first = 0) {
+        check(om_update_triangles(ctx_, first, vertices, n_vertices, indices, n_tri), ctx_);
+    }
+    // updates since the upload; of the last one: triangles rewritten, unbounded, skipped
+    om_update_info update_info() const {
+        om_update_info u{};
+        check(om_get_update_info(ctx_, &u), ctx_);
+        return u;
+    }
 
     // FrozenHittableList::hit (hits.rs:270-334): the closest hit of one ray; false = None, and
     // `rec` is then the miss record (obj 0, t inf).  `dir` is used as given; a unit direction is

@@ -54,6 +54,10 @@ class om_tree_info(C.Structure):               # 32 B
                [("regime", C.c_int32), ("lds_bytes", C.c_uint32)]
 
 
+class om_update_info(C.Structure):             # 16 B
+    _fields_ = [(n, C.c_uint32) for n in ("updates", "triangles", "unbounded", "skipped")]
+
+
 def tree_info_dict(ti):
     """om_tree_info -> dict, the regime by name (TREE_REGIMES)"""
     d = {n: int(getattr(ti, n)) for n, _ in om_tree_info._fields_}
@@ -149,6 +153,7 @@ EXPORTS = [
     "om_world_add_triangles", "om_world_tree_info", "om_get_tree_info",
     "om_path_rng_state", "om_ray_color_device", "om_ray_color", "om_set_path_batch",
     "om_render_rays_device", "om_render_rays",
+    "om_world_update_triangles", "om_update_triangles_device", "om_update_triangles", "om_get_update_info",
 ]
 OM_COMM_ID_BYTES = 128
 OM_TRANSPORT_RCCL, OM_TRANSPORT_LOCAL = 0, 1
@@ -280,6 +285,10 @@ def _load():
         "om_set_path_batch": (st, [vp, C.c_uint32]),
         "om_render_rays_device": (st, [vp, C.POINTER(om_render_params), vp, vp, vp, C.c_uint32, vp, vp]),
         "om_render_rays": (st, [vp, C.POINTER(om_render_params), vp, vp, vp, C.c_uint32, vp, C.POINTER(om_counters)]),
+        "om_world_update_triangles": (st, [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32]),
+        "om_update_triangles_device": (st, [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp]),
+        "om_update_triangles": (st, [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32]),
+        "om_get_update_info": (st, [vp, C.POINTER(om_update_info)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(lib, name)

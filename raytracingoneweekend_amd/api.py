@@ -14,6 +14,7 @@ Names and argument meaning follow the Rust sources so a front-end reads the same
 All arithmetic happens in libottomarcher.so (host f32 builders + HIP kernels);
 this module only marshals arguments.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -272,6 +273,19 @@ class MarchedSdf(Sphere):
 
 
 # ---------------------------------------------------------------- hits.rs
+def _mesh_arrays(what, vertices, faces):
+    """-> contiguous (V, 3) float32 vertices and (T, 3) uint32 faces (or None) of a numpy mesh"""
+    v = np.ascontiguousarray(vertices)
+    if v.dtype != np.float32 or v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f"{what}: vertices must be a (V, 3) float32 array")
+    if faces is None:
+        return v, None
+    f = np.ascontiguousarray(faces)
+    if f.dtype != np.uint32 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"{what}: faces must be a (T, 3) uint32 array")
+    return v, f
+
+
 class HittableList:
     """hits.rs:37-110 — host-side list; `world += prim` appends in type order."""
 
@@ -315,6 +329,18 @@ class HittableList:
             raise TypeError("add_triangles: material must be a Material")
         check(lib.om_world_add_triangles(self._w, v.ctypes.data_as(C.c_void_p), v.shape[0], f.ctypes.data_as(C.c_void_p),
                                          f.shape[0], C.byref(material.raw)))
+        return self
+
+    def update_triangles(self, vertices, faces=None, first=0):
+        """Move triangles of this world (om_world_update_triangles): triangles first .. first + T - 1,
+        in the order they were added, become Triangle.new3points(v[f[k, 0]], v[f[k, 1]], v[f[k, 2]]) and
+        keep their materials and obj ids; without `faces`, triangle k takes vertices 3k, 3k + 1,
+        3k + 2.  All or nothing.  A frozen world made earlier does not change
+        (FrozenHittableList.update_triangles moves that one)."""
+        v, f = _mesh_arrays("update_triangles", vertices, faces)
+        check(lib.om_world_update_triangles(self._w, int(first), v.ctypes.data_as(C.c_void_p), v.shape[0],
+                                            f.ctypes.data_as(C.c_void_p) if f is not None else None,
+                                            f.shape[0] if f is not None else v.shape[0] // 3))
         return self
 
     def clear(self):
@@ -434,6 +460,77 @@ class FrozenHittableList:
         with the stream rules of hit_rays."""
         return self._query("occluded", rays, tmin, tmax, march_steps, windows, out, stream)
 
+    @contextlib.contextmanager
+    def _launch_stream(self, what, device, stream, tensors):
+        """The stream rules of the device forms (hit_rays' docstring) -> the hipStream_t to launch on:
+        `stream` (a non-null handle) or torch's current stream on `device`; when that is the null
+        stream, a side stream of this object ordered with it by events on both sides, on which
+        `tensors` are recorded so that the allocator does not reuse them under the kernel."""
+        import torch
+        if stream is not None and int(stream) == 0:
+            raise ValueError(f"{what}: stream 0 is the ctx's own stream to the library; pass a stream or none")
+        cur = side = None
+        if stream is None:
+            cur = torch.cuda.current_stream(device)
+            stream = cur.cuda_stream
+            if stream == 0:                                       # torch's null stream: order a side stream with it
+                if getattr(self, "_torch_side", None) is None:
+                    self._torch_side = torch.cuda.Stream(device=device)
+                side = self._torch_side
+                side.wait_stream(cur)
+                stream = side.cuda_stream
+        try:
+            yield stream
+        finally:
+            if side is not None:
+                for t in tensors:
+                    t.record_stream(side)
+                cur.wait_stream(side)
+
+    def update_triangles(self, vertices, faces=None, first=0, stream=None):
+        """Move triangles of the uploaded world in place (om_update_triangles /
+        om_update_triangles_device): triangles first .. first + T - 1 (in the order
+        they were added) become Triangle.new3points(v[f[k, 0]], v[f[k, 1]], v[f[k, 2]]); without
+        `faces`, triangle k takes vertices 3k, 3k + 1, 3k + 2.  The trees keep their topology and every
+        box is recomputed, so every later answer is the reference's for the moved mesh.
+
+        numpy in (`vertices` (V, 3) float32, `faces` (T, 3) uint32): synchronous; an index past the
+        last vertex raises and changes nothing.  torch ROCm tensors in ((V, 3) float32, (T, 3) int32
+        or uint32, on this world's device): in place with no host copy, asynchronous, with the stream
+        rules of hit_rays; a face with an index outside the vertices is left as it was and counted
+        in update_info()["skipped"]."""
+        what = "update_triangles"
+        if type(vertices).__module__.split(".")[0] == "torch":
+            import torch
+            v, f = vertices, faces
+            if not v.is_cuda or v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3 or not v.is_contiguous():
+                raise ValueError(f"{what}: need a contiguous (V, 3) float32 tensor on the device")
+            if v.device.index != int(self.device):
+                raise ValueError(f"{what}: vertices are on {v.device}, the world is on device {self.device}")
+            if f is not None:
+                if type(f).__module__.split(".")[0] != "torch" or not f.is_cuda or f.device != v.device or f.dim() != 2 \
+                        or f.shape[1] != 3 or not f.is_contiguous() or f.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                    raise ValueError(f"{what}: faces must be a contiguous (T, 3) int32 / uint32 tensor on the vertices' device")
+            n_tri = f.shape[0] if f is not None else v.shape[0] // 3
+            with self._launch_stream(what, v.device, stream, [v] + ([f] if f is not None else [])) as st:
+                check(lib.om_update_triangles_device(self._ctx, int(first), C.c_void_p(v.data_ptr()), v.shape[0],
+                                                     C.c_void_p(f.data_ptr()) if f is not None else None, n_tri, C.c_void_p(st)),
+                      self._ctx)
+            return self
+        v, f = _mesh_arrays(what, vertices, faces)
+        check(lib.om_update_triangles(self._ctx, int(first), v.ctypes.data_as(C.c_void_p), v.shape[0],
+                                      f.ctypes.data_as(C.c_void_p) if f is not None else None,
+                                      f.shape[0] if f is not None else v.shape[0] // 3), self._ctx)
+        return self
+
+    def update_info(self):
+        """om_get_update_info: updates since the upload, and of the last one the triangles rewritten,
+        those given an all-covering box for a non-finite value (unbounded) and those skipped for an
+        index outside the vertices.  Synchronises like counters()."""
+        u = L.om_update_info()
+        check(lib.om_get_update_info(self._ctx, C.byref(u)), self._ctx)
+        return {n: int(getattr(u, n)) for n, _ in L.om_update_info._fields_}
+
     def _query(self, what, rays, tmin, tmax, march_steps, windows, out, stream):
         occ = what == "occluded"
         q = L.om_query_params(float(tmin), float(tmax), int(march_steps), 0)
@@ -455,36 +552,17 @@ class FrozenHittableList:
             elif type(out).__module__.split(".")[0] != "torch" or not out.is_cuda or out.dtype != dtype \
                     or tuple(out.shape) != shape or not out.is_contiguous() or out.device != rays.device:
                 raise ValueError(f"{what}: out must be a contiguous {shape} {dtype} tensor on the rays' device")
-            if stream is not None and int(stream) == 0:
-                raise ValueError(f"{what}: stream 0 is the ctx's own stream to the library; pass a stream or none")
-            cur = side = None
-            if stream is None:
-                cur = torch.cuda.current_stream(rays.device)
-                stream = cur.cuda_stream
-                if stream == 0:                                   # torch's null stream: order a side stream with it
-                    if getattr(self, "_torch_side", None) is None:
-                        self._torch_side = torch.cuda.Stream(device=rays.device)
-                    side = self._torch_side
-                    side.wait_stream(cur)
-                    stream = side.cuda_stream
             wp = C.c_void_p(windows.data_ptr()) if windows is not None else None
-            try:
+            with self._launch_stream(what, rays.device, stream, [rays, out] + ([windows] if windows is not None else [])) as st:
                 if occ:
                     check(lib.om_occluded_rays_device(self._ctx, C.byref(q), C.c_void_p(rays.data_ptr()), wp, n,
-                                                      C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
+                                                      C.c_void_p(out.data_ptr()), C.c_void_p(st)), self._ctx)
                 elif windows is not None:
                     check(lib.om_hit_rays_windows_device(self._ctx, C.byref(q), C.c_void_p(rays.data_ptr()), wp, n,
-                                                         C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
+                                                         C.c_void_p(out.data_ptr()), C.c_void_p(st)), self._ctx)
                 else:
                     check(lib.om_hit_rays_device(self._ctx, C.byref(q), C.c_void_p(rays.data_ptr()), n,
-                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
-            finally:
-                if side is not None:
-                    rays.record_stream(side)                      # the allocator must not reuse them under the kernel
-                    out.record_stream(side)
-                    if windows is not None:
-                        windows.record_stream(side)
-                    cur.wait_stream(side)
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(st)), self._ctx)
             return out
         a = np.ascontiguousarray(rays)
         if a.dtype == L.RAY_DTYPE:
@@ -559,29 +637,10 @@ class FrozenHittableList:
             elif type(out).__module__.split(".")[0] != "torch" or not out.is_cuda or out.dtype != torch.float32 \
                     or tuple(out.shape) != (n, 5) or not out.is_contiguous() or out.device != rays.device:
                 raise ValueError(f"{what}: out must be a contiguous (n, 5) float32 tensor on the rays' device")
-            if stream is not None and int(stream) == 0:
-                raise ValueError(f"{what}: stream 0 is the ctx's own stream to the library; pass a stream or none")
-            cur = side = None
-            if stream is None:
-                cur = torch.cuda.current_stream(rays.device)
-                stream = cur.cuda_stream
-                if stream == 0:                                   # torch's null stream: order a side stream with it
-                    if getattr(self, "_torch_side", None) is None:
-                        self._torch_side = torch.cuda.Stream(device=rays.device)
-                    side = self._torch_side
-                    side.wait_stream(cur)
-                    stream = side.cuda_stream
             rp = C.c_void_p(rng.data_ptr()) if rng is not None else None
-            try:
+            with self._launch_stream(what, rays.device, stream, [rays, out] + ([rng] if rng is not None else [])) as st:
                 check(lib.om_ray_color_device(self._ctx, C.byref(p), C.c_void_p(rays.data_ptr()), rp, n,
-                                              C.c_void_p(out.data_ptr()), C.c_void_p(stream)), self._ctx)
-            finally:
-                if side is not None:
-                    rays.record_stream(side)
-                    out.record_stream(side)
-                    if rng is not None:
-                        rng.record_stream(side)
-                    cur.wait_stream(side)
+                                              C.c_void_p(out.data_ptr()), C.c_void_p(st)), self._ctx)
             return out
         a = np.ascontiguousarray(rays)
         if a.dtype == L.RAY_DTYPE:
@@ -669,28 +728,10 @@ class FrozenHittableList:
             if pixels is not None and (not pixels.is_cuda or pixels.dtype != torch.int32 or not pixels.is_contiguous()
                                        or pixels.device != rays.device):
                 raise ValueError(f"{what}: pixels must be a contiguous int32 tensor on the rays' device")
-            if stream is not None and int(stream) == 0:
-                raise ValueError(f"{what}: stream 0 is the ctx's own stream to the library; pass a stream or none")
-            cur = side = None
-            if stream is None:
-                cur = torch.cuda.current_stream(rays.device)
-                stream = cur.cuda_stream
-                if stream == 0:                                   # torch's null stream: order a side stream with it
-                    if getattr(self, "_torch_side", None) is None:
-                        self._torch_side = torch.cuda.Stream(device=rays.device)
-                    side = self._torch_side
-                    side.wait_stream(cur)
-                    stream = side.cuda_stream
             ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-            try:
+            with self._launch_stream(what, rays.device, stream, [t for t in (rays, rng, pixels, st) if t is not None]) as hs:
                 check(lib.om_render_rays_device(self._ctx, C.byref(p), ptr(rays), ptr(rng), ptr(pixels), n, ptr(st),
-                                                C.c_void_p(stream)), self._ctx)
-            finally:
-                if side is not None:
-                    for t in (rays, rng, pixels, st):
-                        if t is not None:
-                            t.record_stream(side)
-                    cur.wait_stream(side)
+                                                C.c_void_p(hs)), self._ctx)
             return None
         buf = pixels_box.pixels if isinstance(pixels_box, PixelsBox) else pixels_box
         if not isinstance(buf, np.ndarray) or buf.dtype != L.PIXEL_STATS_DTYPE or buf.size != W * H \

@@ -32,35 +32,8 @@
 namespace om {
 namespace {
 
-struct Box {
-    double lo[3], hi[3];
-    void empty() { for (int i = 0; i < 3; ++i) { lo[i] = 1e300; hi[i] = -1e300; } }
-    void grow(const Box& b) { for (int i = 0; i < 3; ++i) { lo[i] = std::min(lo[i], b.lo[i]); hi[i] = std::max(hi[i], b.hi[i]); } }
-    void grow_pt(const double* p) { for (int i = 0; i < 3; ++i) { lo[i] = std::min(lo[i], p[i]); hi[i] = std::max(hi[i], p[i]); } }
-    double area() const {
-        const double dx = std::max(0.0, hi[0] - lo[0]), dy = std::max(0.0, hi[1] - lo[1]), dz = std::max(0.0, hi[2] - lo[2]);
-        return 2.0 * (dx * dy + dy * dz + dz * dx);
-    }
-};
-
+// (Box, inflate, bary_box and the outward f32 planes: om_refit.h, shared with the refit kernels)
 struct Item { Box b; double c[3]; uint32_t gi; };
-
-// Inflate a box beyond the f32 rounding of the exact tests at the scene scale.  The margin is
-// absolute; Sphere::hit accepts rays that pass an ellipsoid at up to about 6e-8 * (D^2 + C*D) / (2r)
-// outside it (ray origin D away, world coordinates up to C, smallest semi-axis r), which passes
-// this margin for r = 0.2 from D of about 100 on and for r <= 9e-3 at D = 13 (thin_sphere below keeps
-// out of the trees what the worst case of that error can reach from OM_SPHERE_REACH away): DESIGN.md §5.3 states the domain, tests/test_scale_conservative.py measures
-// it from these very boxes.
-Box inflate(Box b) {
-    double mag = 0.0;
-    for (int i = 0; i < 3; ++i) mag = std::max(mag, std::max(std::fabs(b.lo[i]), std::fabs(b.hi[i])));
-    for (int i = 0; i < 3; ++i) {
-        const double ext = b.hi[i] - b.lo[i];
-        const double m = 1e-3 * (1.0 + ext) + 1e-5 * mag;
-        b.lo[i] -= m; b.hi[i] += m;
-    }
-    return b;
-}
 
 Box affine_box(const Mat4& l2w, double half) {
     Box b;
@@ -73,20 +46,6 @@ Box affine_box(const Mat4& l2w, double half) {
     return inflate(b);
 }
 
-Box bary_box(const BaryPrim& p, bool para) {
-    Box b; b.empty();
-    double o[3], pu[3], pv[3], puv[3];
-    for (int i = 0; i < 3; ++i) {
-        o[i] = p.origin.e[i];
-        pu[i] = o[i] + (double)p.u.e[i] * p.u_length;
-        pv[i] = o[i] + (double)p.v.e[i] * p.v_length;
-        puv[i] = pu[i] + (double)p.v.e[i] * p.v_length;
-    }
-    b.grow_pt(o); b.grow_pt(pu); b.grow_pt(pv);
-    if (para) b.grow_pt(puv);
-    return inflate(b);
-}
-
 struct Builder {
     std::vector<Item> items;
     std::vector<OmBvhNode> nodes;
@@ -95,10 +54,7 @@ struct Builder {
 
     uint32_t emit(const Box& b) {
         OmBvhNode n;
-        for (int i = 0; i < 3; ++i) {
-            n.lo[i] = std::nextafter((float)b.lo[i], -INFINITY);
-            n.hi[i] = std::nextafter((float)b.hi[i], INFINITY);
-        }
+        box_planes(b, n.lo, n.hi);
         n.left = 0; n.right = 0;
         nodes.push_back(n);
         return (uint32_t)(nodes.size() - 1);
@@ -181,28 +137,6 @@ struct Builder {
 
 }  // namespace
 
-// IEEE half bits -> the value, exactly (every half is a float).
-float half_value(uint16_t h) {
-    const int e = (h >> 10) & 31, m = h & 1023;
-    const float v = e == 0 ? std::ldexp((float)m, -24) : e == 31 ? INFINITY : std::ldexp((float)(1024 + m), e - 25);
-    return (h & 0x8000u) ? -v : v;
-}
-
-// The half-precision plane that contains x on the outside: the largest half <= x (up = false, a
-// box's lo) or the smallest half >= x (up = true, its hi); +-inf beyond the half range.  Binary
-// search over the halves in value order (key k >= 0: bits k; k < 0: the negative half -k).
-uint16_t half_out(float x, bool up) {
-    auto bits = [](int k) { return (uint16_t)(k >= 0 ? k : (0x8000 | -k)); };
-    if (std::isnan(x)) return bits(up ? 0x7C00 : -0x7C00);
-    int lo = -0x7C00, hi = 0x7C00;                       // -inf .. +inf
-    if (!up) {                                           // largest k with value(k) <= x
-        while (lo < hi) { const int mid = lo + (hi - lo + 1) / 2; if (half_value(bits(mid)) <= x) lo = mid; else hi = mid - 1; }
-        return bits(lo);
-    }
-    while (lo < hi) { const int mid = lo + (hi - lo) / 2; if (half_value(bits(mid)) >= x) hi = mid; else lo = mid + 1; }
-    return bits(lo);
-}
-
 
 // Smallest and largest semi-axis of an ellipsoid: the extreme singular values of the 3x3 linear
 // part (closed form for the eigenvalues of the symmetric A^T A, in double).
@@ -279,10 +213,8 @@ Selection select(const om_world& w, const FrozenWorld& fw, bool leaf_trees) {
             if (m[1] == 0.0f && m[2] == 0.0f && m[4] == 0.0f && m[6] == 0.0f && m[8] == 0.0f && m[9] == 0.0f)
                 r.pad = OM_ALWAYS_DIAG_SPHERE;
         }
-        for (int i = 0; i < 3; ++i) {
-            r.lo[i] = box ? std::nextafter((float)box->lo[i], -INFINITY) : -INFINITY;
-            r.hi[i] = box ? std::nextafter((float)box->hi[i], INFINITY) : INFINITY;
-        }
+        if (box) box_planes(*box, r.lo, r.hi);
+        else for (int i = 0; i < 3; ++i) { r.lo[i] = -INFINITY; r.hi[i] = INFINITY; }
         s.always.push_back(r);
     };
     auto add = [&](const Box& box, uint32_t gi, bool thin, bool boxed_outside) {
@@ -365,11 +297,11 @@ Tree build_tree(std::vector<Item> items) {
 }
 
 // The global BVH over every bounded traced primitive: bvh, bvh_prims, always.
-void build_global(const om_world& w, FrozenWorld& fw) {
+void build_global(const om_world& w, FrozenWorld& fw, Selection& s, bool keep) {
     Builder b;
-    Selection s = select(w, fw, false);
+    s = select(w, fw, false);
     for (const OmAlwaysRec& r : s.always) fw.always.push_back(r.gi);
-    b.items.swap(s.items);
+    if (keep) b.items = s.items; else b.items.swap(s.items);     // keep: the refit tables read the selection afterwards
     if (b.items.empty()) return;
     Tree t = sah_tree(b, OM_BVH_MAX_LEAF, OM_BVH_LEAF_FORCE);
     fw.bvh.swap(t.nodes);
@@ -379,11 +311,12 @@ void build_global(const om_world& w, FrozenWorld& fw) {
 // Stage 3, the stackless layout: the tree re-emitted in depth-first order with a skip
 // ("miss") link per node (snodes), and the primitives' test records copied in leaf order so a leaf
 // owns a contiguous run (srecs, n_srec_bary).  -> per builder node, the first record of a leaf
-std::vector<uint32_t> emit_skip(const Tree& t, FrozenWorld& fw) {
+std::vector<uint32_t> emit_skip(const Tree& t, FrozenWorld& fw, std::vector<uint32_t>* src) {
     std::vector<uint32_t> leaf_first(t.nodes.size(), 0);
     struct Emit {
-        const Tree& t; FrozenWorld& fw; std::vector<uint32_t>& leaf_first;
+        const Tree& t; FrozenWorld& fw; std::vector<uint32_t>& leaf_first; std::vector<uint32_t>* src;
         void rec(uint32_t n) {
+            if (src) src->push_back(n);
             const OmBvhNode& src = t.nodes[n];
             const uint32_t idx = (uint32_t)fw.snodes.size();
             OmSkipNode o;
@@ -410,7 +343,7 @@ std::vector<uint32_t> emit_skip(const Tree& t, FrozenWorld& fw) {
             }
             fw.snodes[idx].skip = (uint32_t)fw.snodes.size();
         }
-    } e{t, fw, leaf_first};
+    } e{t, fw, leaf_first, src};
     e.rec(0u);
     return leaf_first;
 }
@@ -421,7 +354,8 @@ std::vector<uint32_t> emit_skip(const Tree& t, FrozenWorld& fw) {
 // child k's box in a node, `leaf` makes the code of a leaf child from its (first record, count).  A
 // single leaf becomes one node whose second child is an empty leaf.
 template <class Node, class BoxFn, class LeafFn>
-void emit_bvh2(const Tree& t, const std::vector<uint32_t>& leaf_first, std::vector<Node>& out, BoxFn box, LeafFn leaf) {
+void emit_bvh2(const Tree& t, const std::vector<uint32_t>& leaf_first, std::vector<Node>& out, BoxFn box, LeafFn leaf,
+               std::vector<uint32_t>* box_src = nullptr) {
     OmBvhNode none{};
     for (int i = 0; i < 3; ++i) { none.lo[i] = INFINITY; none.hi[i] = -INFINITY; }
     const bool one = t.nodes[0].left < 0;
@@ -441,6 +375,11 @@ void emit_bvh2(const Tree& t, const std::vector<uint32_t>& leaf_first, std::vect
         o.c0 = code(one ? 0u : (uint32_t)src.left);
         o.c1 = one ? leaf(0u, 0u) : code((uint32_t)src.right);
         out[q[h].second] = o;
+        if (box_src) {                                        // per output node: the builder nodes of its two boxes
+            if (box_src->size() < 2u * out.size()) box_src->resize(2u * out.size(), kRefitNoNode);
+            (*box_src)[2u * q[h].second] = one ? 0u : (uint32_t)t.nodes[q[h].first].left;
+            (*box_src)[2u * q[h].second + 1u] = one ? kRefitNoNode : (uint32_t)t.nodes[q[h].first].right;
+        }
     }
 }
 
@@ -450,7 +389,7 @@ void emit_bvh2(const Tree& t, const std::vector<uint32_t>& leaf_first, std::vect
 // OM_LEAF | first << 4 | count, so the traversal needs no leaf-table read to enter a leaf; the table
 // is still emitted (same order) for the other consumers.  (Both conditions checked here, not assumed
 // from the builder's leaf cap: a larger count would spill into the `first` bits)
-void emit_b2(const Tree& t, const std::vector<uint32_t>& leaf_first, FrozenWorld& fw) {
+void emit_b2(const Tree& t, const std::vector<uint32_t>& leaf_first, FrozenWorld& fw, std::vector<uint32_t>* src) {
     const bool direct = fw.srecs.size() < kDirectFirst16 && t.max_leaf <= kLeafCountMax;
     fw.b2_direct = direct ? 1u : 0u;
     emit_bvh2(t, leaf_first, fw.b2nodes,
@@ -460,7 +399,7 @@ void emit_b2(const Tree& t, const std::vector<uint32_t>& leaf_first, FrozenWorld
               [&](uint32_t first, uint32_t cnt) {
                   fw.b2leaves.push_back((first << 8) | cnt);
                   return OM_LEAF | (direct ? (first << kLeafCountBits) | cnt : (uint32_t)(fw.b2leaves.size() - 1));
-              });
+              }, src);
 }
 
 // The half-precision copy of b2nodes (b2h).
@@ -498,8 +437,9 @@ void emit_srec_box(const om_world& w, FrozenWorld& fw) {
                                                                        : bary_box(w.triangles[gi - fw.offsets[K_TRI]], false))
                      : (tag & OM_REC_CUBE) ? affine_box(w.cubes[gi - fw.offsets[K_CUBE]].l2w, 0.5)
                                            : affine_box(w.spheres[gi].l2w, -1.0);
-        for (int i = 0; i < 3; ++i) fw.srec_box.push_back(std::nextafter((float)bx.lo[i], -INFINITY));
-        for (int i = 0; i < 3; ++i) fw.srec_box.push_back(std::nextafter((float)bx.hi[i], INFINITY));
+        float p[6];
+        box_planes(bx, p, p + 3);
+        fw.srec_box.insert(fw.srec_box.end(), p, p + 6);
     }
 }
 
@@ -507,12 +447,13 @@ void emit_srec_box(const om_world& w, FrozenWorld& fw) {
 // children and keeps replacing the internal child of largest surface area by that child's two children,
 // up to four.  Child boxes are the BVH2's (already conservative), so culling stays exact.  Collapsed
 // from the 16-bit codes of b2nodes: none for a tree past them.
-void build_bvh4(FrozenWorld& fw) {
+void build_bvh4(FrozenWorld& fw, RefitTables* rt) {
     if (fw.b2nodes.empty() || fw.b2nodes.size() >= kCode16Limit || fw.b2leaves.size() >= kCode16Limit) return;
-    struct Ch { uint32_t code; float lo[3], hi[3]; };
+    struct Ch { uint32_t code; float lo[3], hi[3]; uint32_t src; };      // src: the builder node of the box (refit)
     auto kids = [&](uint32_t n, Ch* out) {
         const OmBvh2Node& N = fw.b2nodes[n];
         out[0].code = N.c0; out[1].code = N.c1;
+        out[0].src = rt ? rt->b2_src[2u * n] : kRefitNoNode; out[1].src = rt ? rt->b2_src[2u * n + 1u] : kRefitNoNode;
         for (int i = 0; i < 3; ++i) {
             out[0].lo[i] = OM_B2_LO(N, 0, i); out[0].hi[i] = OM_B2_HI(N, 0, i);
             out[1].lo[i] = OM_B2_LO(N, 1, i); out[1].hi[i] = OM_B2_HI(N, 1, i);
@@ -524,7 +465,7 @@ void build_bvh4(FrozenWorld& fw) {
         return dx * dy + dy * dz + dz * dx;
     };
     struct Rec {
-        FrozenWorld& fw; decltype(kids)& kids_of; decltype(area)& area_of;
+        FrozenWorld& fw; decltype(kids)& kids_of; decltype(area)& area_of; RefitTables* rt;
         uint32_t go(uint32_t n2, uint32_t depth) {
             std::vector<Ch> ch(2);
             kids_of(n2, ch.data());
@@ -553,9 +494,13 @@ void build_bvh4(FrozenWorld& fw) {
                 }
             }
             fw.b4nodes[idx] = o;
+            if (rt) {
+                if (rt->b4_src.size() < 4u * fw.b4nodes.size()) rt->b4_src.resize(4u * fw.b4nodes.size(), kRefitNoNode);
+                for (size_t k = 0; k < ch.size(); ++k) rt->b4_src[4u * idx + k] = ch[k].src;
+            }
             return idx;
         }
-    } r{fw, kids, area};
+    } r{fw, kids, area, rt};
     r.go(0, 1);
     // breadth-first renumbering with half-precision planes (trees read through L2, §5.7)
     std::vector<uint32_t> order{0u}, pos(fw.b4nodes.size(), 0u);
@@ -572,20 +517,64 @@ void build_bvh4(FrozenWorld& fw) {
             o.child[k] = (c == OM_EMPTY || (c & OM_LEAF)) ? c : (uint16_t)pos[c];
         }
         fw.b4h.push_back(o);
+        if (rt) rt->b4h_src.insert(rt->b4h_src.end(), rt->b4_src.begin() + 4u * n, rt->b4_src.begin() + 4u * n + 4u);
     }
+}
+
+// What a refit of the uploaded world needs (om_refit.h), from the stages' own data: the box of every
+// primitive that is an item of a tree or a boxed record outside, the two topologies by depth, and
+// per stored box of every layout its builder node (the src arrays the stages filled).
+void keep_for_refit(const FrozenWorld& fw, const Selection& global, const Selection& leaf, const Tree* t,
+                    const std::vector<uint32_t>& leaf_first, RefitTables& rt) {
+    const uint32_t n_traced = fw.offsets[K_MSPHERE];
+    rt.covering = n_traced;
+    rt.tri_first = fw.offsets[K_TRI];
+    rt.prim_box.resize(6u * ((size_t)n_traced + 1u));
+    for (uint32_t gi = 0; gi < n_traced; ++gi) box_none(&rt.prim_box[6u * (size_t)gi]);
+    box_covering(&rt.prim_box[6u * (size_t)n_traced]);
+    auto keep = [&](uint32_t gi, const float* lo, const float* hi) {
+        bool ok = true;
+        for (int i = 0; i < 3; ++i) ok = ok && finite_f32(lo[i]) && finite_f32(hi[i]);
+        if (!ok) return;                     // unbounded outside, or an item the unions' min / max skip
+        for (int i = 0; i < 3; ++i) { rt.prim_box[6u * (size_t)gi + i] = lo[i]; rt.prim_box[6u * (size_t)gi + 3 + i] = hi[i]; }
+    };
+    for (const Selection* s : {&global, &leaf}) {
+        for (const Item& it : s->items) { float p[6]; box_planes(it.b, p, p + 3); keep(it.gi, p, p + 3); }
+        for (const OmAlwaysRec& r : s->always) keep(r.gi, r.lo, r.hi);
+    }
+    refit_levels(fw.bvh, rt.g_level, rt.g_level_off);
+    rt.tri_rec.assign(fw.counts[K_TRI], kRefitNoNode);
+    if (!t) return;
+    rt.tnodes = t->nodes;
+    for (size_t n = 0; n < rt.tnodes.size(); ++n)
+        if (rt.tnodes[n].left < 0) rt.tnodes[n].left = -(int32_t)(leaf_first[n] + 1u);      // items: the leaf's records
+    for (size_t r = 0; r < fw.srecs.size(); ++r) {
+        uint32_t tag;
+        std::memcpy(&tag, &fw.srecs[r].pad, 4);
+        const uint32_t gi = tag & OM_REC_GI;
+        rt.titems.push_back(gi);
+        if (gi >= fw.offsets[K_TRI] && gi < fw.offsets[K_TRI + 1]) rt.tri_rec[gi - fw.offsets[K_TRI]] = (uint32_t)r;
+    }
+    refit_levels(rt.tnodes, rt.t_level, rt.t_level_off);
 }
 
 }  // namespace
 
-void build_bvh(const om_world& w, FrozenWorld& fw) {
-    build_global(w, fw);
+void build_bvh(const om_world& w, FrozenWorld& fw, RefitTables* rt) {
+    if (rt) *rt = RefitTables();
+    if (w.triangles.empty()) rt = nullptr;          // nothing can move
+    Selection g;
+    build_global(w, fw, g, rt != nullptr);
     Selection s = select(w, fw, true);
     for (const OmAlwaysRec& r : s.always) fw.always2.push_back(r.gi);
-    fw.always2_rec.swap(s.always);
-    if (s.items.empty()) return;
-    const Tree t = build_tree(std::move(s.items));
-    const std::vector<uint32_t> leaf_first = emit_skip(t, fw);
-    emit_b2(t, leaf_first, fw);
+    if (rt) fw.always2_rec = s.always; else fw.always2_rec.swap(s.always);
+    if (s.items.empty()) {
+        if (rt) keep_for_refit(fw, g, s, nullptr, {}, *rt);
+        return;
+    }
+    const Tree t = rt ? build_tree(s.items) : build_tree(std::move(s.items));
+    const std::vector<uint32_t> leaf_first = emit_skip(t, fw, rt ? &rt->snode_src : nullptr);
+    emit_b2(t, leaf_first, fw, rt ? &rt->b2_src : nullptr);
     emit_b2h(fw);
     emit_b2w(t, leaf_first, fw);
     // the traversals' stack bounds: a single leaf still takes one node
@@ -593,7 +582,8 @@ void build_bvh(const om_world& w, FrozenWorld& fw) {
     fw.b2w_depth = fw.b2w.empty() ? 0u : fw.b2_depth;
     fw.b2_max_leaf = t.max_leaf;
     emit_srec_box(w, fw);
-    build_bvh4(fw);
+    build_bvh4(fw, rt);
+    if (rt) keep_for_refit(fw, g, s, &t, leaf_first, *rt);
 }
 
 }  // namespace om

@@ -9,13 +9,10 @@
 #include "om_world.h"
 
 namespace om {
-void build_bvh(const om_world& w, FrozenWorld& fw);
+void build_bvh(const om_world& w, FrozenWorld& fw, RefitTables* rt = nullptr);
 // a sphere / ellipsoid whose test's error from OM_SPHERE_REACH away can pass its margin: outside every
 // tree, no `culled` bound (§5.3)
 bool thin_sphere(const Mat4& l2w);
-// the half-precision node planes (OmBvh2NodeH): a half's exact value, and the half that holds a
-// float plane on the outside (lo: the largest half <= x, hi: the smallest half >= x; NaN -> the
-// infinite plane, so a NaN box culls nothing)
-float half_value(uint16_t h);
-uint16_t half_out(float x, bool up);
+// (the half-precision node planes, half_value and half_out, are in om_refit.h: the refit kernels round
+// with them too)
 }

@@ -8,27 +8,37 @@
 #include <cmath>
 #include <cstdint>
 
+// the Vec3 / Mat3 pieces also run in the refit kernels (om_refit.hip: the same f32 operations in the
+// same order, correctly rounded on the device too)
+#ifndef OM_HD
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define OM_HD __host__ __device__
+#else
+#define OM_HD
+#endif
+#endif
+
 namespace om {
 
 struct Vec3 {
     float e[3];
-    float x() const { return e[0]; }
-    float y() const { return e[1]; }
-    float z() const { return e[2]; }
-    static Vec3 make(float x, float y, float z) { Vec3 v; v.e[0] = x; v.e[1] = y; v.e[2] = z; return v; }
-    static Vec3 load(const float* p) { return make(p[0], p[1], p[2]); }
-    void store(float* p) const { p[0] = e[0]; p[1] = e[1]; p[2] = e[2]; }
-    Vec3 neg() const { return make(-e[0], -e[1], -e[2]); }                               // vec3.rs:118-121
-    Vec3 add(const Vec3& o) const { return make(e[0] + o.e[0], e[1] + o.e[1], e[2] + o.e[2]); }  // vec3.rs:184-193
-    Vec3 sub(const Vec3& o) const { return add(o.neg()); }                               // vec3.rs:194-199
-    Vec3 mul(const Vec3& o) const { return make(e[0] * o.e[0], e[1] * o.e[1], e[2] * o.e[2]); }  // vec3.rs:200-209
-    Vec3 scale(float s) const { return make(e[0] * s, e[1] * s, e[2] * s); }             // vec3.rs:220-235
-    Vec3 div(float s) const { return scale(1.0f / s); }                                  // vec3.rs:236-240
-    float dot(const Vec3& o) const { return e[0] * o.e[0] + e[1] * o.e[1] + e[2] * o.e[2]; }  // vec3.rs:29-31
-    float length_squared() const { return dot(*this); }
-    float length() const { return std::sqrt(length_squared()); }
-    Vec3 unit() const { return div(length()); }                                          // vec3.rs:38-40
-    Vec3 cross(const Vec3& o) const {                                                    // vec3.rs:62-68
+    OM_HD float x() const { return e[0]; }
+    OM_HD float y() const { return e[1]; }
+    OM_HD float z() const { return e[2]; }
+    OM_HD static Vec3 make(float x, float y, float z) { Vec3 v; v.e[0] = x; v.e[1] = y; v.e[2] = z; return v; }
+    OM_HD static Vec3 load(const float* p) { return make(p[0], p[1], p[2]); }
+    OM_HD void store(float* p) const { p[0] = e[0]; p[1] = e[1]; p[2] = e[2]; }
+    OM_HD Vec3 neg() const { return make(-e[0], -e[1], -e[2]); }                               // vec3.rs:118-121
+    OM_HD Vec3 add(const Vec3& o) const { return make(e[0] + o.e[0], e[1] + o.e[1], e[2] + o.e[2]); }  // vec3.rs:184-193
+    OM_HD Vec3 sub(const Vec3& o) const { return add(o.neg()); }                               // vec3.rs:194-199
+    OM_HD Vec3 mul(const Vec3& o) const { return make(e[0] * o.e[0], e[1] * o.e[1], e[2] * o.e[2]); }  // vec3.rs:200-209
+    OM_HD Vec3 scale(float s) const { return make(e[0] * s, e[1] * s, e[2] * s); }             // vec3.rs:220-235
+    OM_HD Vec3 div(float s) const { return scale(1.0f / s); }                                  // vec3.rs:236-240
+    OM_HD float dot(const Vec3& o) const { return e[0] * o.e[0] + e[1] * o.e[1] + e[2] * o.e[2]; }  // vec3.rs:29-31
+    OM_HD float length_squared() const { return dot(*this); }
+    OM_HD float length() const { return std::sqrt(length_squared()); }
+    OM_HD Vec3 unit() const { return div(length()); }                                          // vec3.rs:38-40
+    OM_HD Vec3 cross(const Vec3& o) const {                                                    // vec3.rs:62-68
         return make(e[1] * o.e[2] - e[2] * o.e[1], e[2] * o.e[0] - e[0] * o.e[2], e[0] * o.e[1] - e[1] * o.e[0]);
     }
 };
@@ -44,16 +54,16 @@ struct Vec4 {
 
 struct Mat3 {
     Vec3 r[3];
-    float at(int i, int j) const { return r[i].e[j]; }
-    static Mat3 rows(const Vec3& a, const Vec3& b, const Vec3& c) { Mat3 m; m.r[0] = a; m.r[1] = b; m.r[2] = c; return m; }
-    static Mat3 cols(const Vec3& a, const Vec3& b, const Vec3& c) {                     // mat3x3.rs:22-26
+    OM_HD float at(int i, int j) const { return r[i].e[j]; }
+    OM_HD static Mat3 rows(const Vec3& a, const Vec3& b, const Vec3& c) { Mat3 m; m.r[0] = a; m.r[1] = b; m.r[2] = c; return m; }
+    OM_HD static Mat3 cols(const Vec3& a, const Vec3& b, const Vec3& c) {                     // mat3x3.rs:22-26
         return rows(Vec3::make(a.x(), b.x(), c.x()), Vec3::make(a.y(), b.y(), c.y()), Vec3::make(a.z(), b.z(), c.z()));
     }
-    Vec3 apply(const Vec3& v) const { return Vec3::make(r[0].dot(v), r[1].dot(v), r[2].dot(v)); }  // mat3x3.rs:27-29
-    Mat3 transpose() const {                                                             // mat3x3.rs:49-51
+    OM_HD Vec3 apply(const Vec3& v) const { return Vec3::make(r[0].dot(v), r[1].dot(v), r[2].dot(v)); }  // mat3x3.rs:27-29
+    OM_HD Mat3 transpose() const {                                                             // mat3x3.rs:49-51
         return rows(Vec3::make(at(0, 0), at(1, 0), at(2, 0)), Vec3::make(at(0, 1), at(1, 1), at(2, 1)), Vec3::make(at(0, 2), at(1, 2), at(2, 2)));
     }
-    float determinant() const {                                                          // mat3x3.rs:52-68 (Kahan)
+    OM_HD float determinant() const {                                                          // mat3x3.rs:52-68 (Kahan)
         const float terms[6] = {at(0, 0) * at(1, 1) * at(2, 2), at(0, 1) * at(1, 2) * at(2, 0), at(0, 2) * at(1, 0) * at(2, 1),
                                 -at(0, 0) * at(1, 2) * at(2, 1), -at(0, 1) * at(1, 0) * at(2, 2), -at(0, 2) * at(1, 1) * at(2, 0)};
         float sum = 0.0f, comp = 0.0f;
@@ -65,7 +75,7 @@ struct Mat3 {
         }
         return sum;
     }
-    Mat3 inverse() const {                                                               // mat3x3.rs:69-81, 92-96
+    OM_HD Mat3 inverse() const {                                                               // mat3x3.rs:69-81, 92-96
         const float det = determinant();
         const float s = 1.0f / det;
         const Vec3 a = Vec3::make(at(1, 1) * at(2, 2) - at(1, 2) * at(2, 1), at(0, 2) * at(2, 1) - at(0, 1) * at(2, 2),

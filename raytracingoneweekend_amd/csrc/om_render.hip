@@ -20,6 +20,7 @@
 #include "om_wavefront.h"
 #include "om_world.h"
 #include "om_internal.h"
+#include "om_refit_dev.h"
 
 using namespace omd;
 
@@ -85,6 +86,19 @@ struct om_ctx {
     DevBuf path_rng, path_out;          // om_ray_color staging (the rays go through query_rays)
     uint32_t path_batch_log2 = 0;       // om_set_path_batch (0 = default)
     uint32_t frame_w = 0, frame_h = 0;
+    // om_update_triangles (om_refit.hip): the uploaded world's refit tables (their
+    // buffers are scene_bufs), staging of the host form, and what the host keeps of the boxes: the
+    // root box comes back through a pinned node after each update (root_ev: that copy; two of each,
+    // used in turn, so that an update does not wait on the host for the one before it), the record
+    // boxes of the tile lists are fetched when the next lists are built (boxes_stale)
+    omr::Tables refit;
+    DevBuf upd_vertices, upd_indices;
+    OmBvhNode* root_host = nullptr;       // two nodes
+    hipEvent_t root_ev[2] = {nullptr, nullptr};
+    uint32_t root_slot = 0;               // the slot of the last update
+    bool root_used[2] = {false, false};   // a copy into the slot has been queued
+    bool root_pending = false, boxes_stale = false;
+    om_update_info update_info{};
     ~om_ctx() {
         for (auto& b : scene_bufs) b.release();
         for (auto& j : jitters) j.buf.release();
@@ -95,6 +109,9 @@ struct om_ctx {
         view_scratch.release(); view_rgb.release(); tile_off.release(); tile_idx.release(); tile_tnear.release();
         wf.release();
         timer.release();
+        upd_vertices.release(); upd_indices.release();
+        if (root_host) (void)hipHostFree(root_host);
+        for (hipEvent_t e : root_ev) if (e) (void)hipEventDestroy(e);
         if (progress_host) (void)hipHostFree(progress_host);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -197,6 +214,16 @@ om_status ensure_tile_lists(om_ctx* c, const om_camera* cam, uint32_t W, uint32_
     const bool same = c->tiles_valid && c->tiles_gen == c->world_gen && c->tiles_w == W && c->tiles_h == H &&
                       std::memcmp(&c->tiles_cam, cam, sizeof(om_camera)) == 0;
     if (!same) {
+        if (c->boxes_stale) {       // an update moved boxes: the records' own, from the device
+            std::vector<float> pb((size_t)c->refit.n_prim * 6u);
+            std::vector<uint32_t> items(c->refit.n_titems);
+            OM_HIP(c, hipStreamSynchronize(stream));
+            if (c->last_stream && c->last_stream != stream) OM_HIP(c, hipStreamSynchronize(c->last_stream));
+            OM_HIP(c, hipMemcpy(pb.data(), c->refit.prim_box, pb.size() * 4u, hipMemcpyDeviceToHost));
+            if (!items.empty()) OM_HIP(c, hipMemcpy(items.data(), c->refit.titems, items.size() * 4u, hipMemcpyDeviceToHost));
+            for (size_t r = 0; r < items.size(); ++r) std::copy_n(pb.begin() + 6u * (size_t)items[r], 6, c->srec_box.begin() + 6u * r);
+            c->boxes_stale = false;
+        }
         omt::TileLists tl;
         const bool ok = omt::build(c->srec_box, *cam, W, H, tl);
         // the cache keys are set only once the device lists are complete: a failed upload
@@ -290,6 +317,12 @@ om_status launch(om_ctx* c, const om_camera* cam, const om_render_params* p, om_
     // om_wavefront.hip, against the box of the bounded primitives) renders with the reference loop:
     // out there the slab test is no finer than the box inflation.  Decided per call
     // on the host; no other frame runs anything else.
+    if (c->root_pending) {          // the last update's root box (its copy is queued behind the refit)
+        const OmBvhNode& root = c->root_host[c->root_slot];
+        OM_HIP(c, hipEventSynchronize(c->root_ev[c->root_slot]));
+        for (int i = 0; i < 3; ++i) { c->root_box[i] = root.lo[i]; c->root_box[3 + i] = root.hi[i]; }
+        c->root_pending = false;
+    }
     if (c->have_root && beyond_slab_reach(c->root_box, c->root_box + 3, cam->origin[0], cam->origin[1], cam->origin[2]))
         mode = OM_KERNEL_BRUTE;
     L.S = c->scene;
@@ -377,7 +410,12 @@ om_status om_upload_world(om_ctx* c, const om_world* w) {
     c->scene_bufs.clear();
     c->have_world = false;
     om::FrozenWorld fw;
-    w->freeze(fw);
+    om::RefitTables rt;
+    w->freeze(fw, &rt);
+    c->refit = omr::Tables();
+    c->root_pending = false; c->boxes_stale = false;
+    c->root_used[0] = c->root_used[1] = false;       // (the stream was synchronised above: no copy is in flight)
+    c->update_info = om_update_info{};
     OmSceneDev& S = c->scene;
     S = OmSceneDev{};
     om_status s = OM_OK;
@@ -427,12 +465,119 @@ om_status om_upload_world(om_ctx* c, const om_world* w) {
     S.b4_stack = plan.b4_stack; S.b4_lds_bytes = plan.b4_lds_bytes;
     S.n_b2wnodes = plan.n_b2wnodes; S.b2w_stack = plan.b2w_stack;
     om::fill_tree_info(fw, plan, &c->tree_info);
+    if (!rt.empty()) {              // worlds with triangles: what om_update_triangles needs
+        omr::Tables& T = c->refit;
+        const float* prim_box = nullptr; const uint32_t *tri_rec = nullptr, *g_level = nullptr, *titems = nullptr, *t_level = nullptr,
+                                                        *snode_src = nullptr, *b2_src = nullptr, *b4_src = nullptr, *b4h_src = nullptr;
+        const OmBvhNode* tnodes = nullptr;
+#define UPT(vec) if ((s = upload(c, rt.vec, &vec)) != OM_OK) return s
+        UPT(prim_box); UPT(tri_rec); UPT(g_level); UPT(tnodes); UPT(titems); UPT(t_level); UPT(snode_src); UPT(b2_src);
+        if (plan.b4_ok) { UPT(b4_src); UPT(b4h_src); }
+#undef UPT
+        DevBuf info;
+        info.n = omr::kInfoWords * sizeof(uint32_t);
+        OM_HIP(c, hipMalloc(&info.p, info.n));
+        c->scene_bufs.push_back(info);
+        OM_HIP(c, hipMemsetAsync(info.p, 0, info.n, c->stream));
+        T.prim_box = (float*)prim_box; T.n_prim = (uint32_t)(rt.prim_box.size() / 6u); T.covering = rt.covering;
+        T.tri_first = rt.tri_first; T.n_tri = fw.counts[om::K_TRI]; T.tri_rec = (uint32_t*)tri_rec;
+        T.g_level = (uint32_t*)g_level; T.g_level_off = rt.g_level_off;
+        T.tnodes = (OmBvhNode*)tnodes; T.n_tnodes = (uint32_t)rt.tnodes.size();
+        T.titems = (uint32_t*)titems; T.n_titems = (uint32_t)rt.titems.size();
+        T.t_level = (uint32_t*)t_level; T.t_level_off = rt.t_level_off;
+        T.snode_src = (uint32_t*)snode_src; T.n_snode = (uint32_t)rt.snode_src.size();
+        T.b2_src = (uint32_t*)b2_src; T.n_b2 = (uint32_t)fw.b2nodes.size();
+        T.n_b2h = plan.b2_ok ? T.n_b2 : 0u; T.n_b2w = plan.b2w_ok ? T.n_b2 : 0u;
+        T.b4_src = (uint32_t*)b4_src; T.b4h_src = (uint32_t*)b4h_src; T.n_b4 = plan.b4_ok ? (uint32_t)fw.b4nodes.size() : 0u;
+        T.info = (uint32_t*)info.p;
+        if (!c->root_host) OM_HIP(c, hipHostMalloc((void**)&c->root_host, 2u * sizeof(OmBvhNode), hipHostMallocDefault));
+        for (hipEvent_t& e : c->root_ev) if (!e) OM_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
     // barycentric leaf records carry gi in 30 bits beside the two kind bits (om_layout.h OM_REC_GI)
     S.n_srec_bary = fw.n_srec_bary;
     if (fw.n_srec_bary && fw.offsets[om::K_N] > OM_REC_GI)
         return set_err(c, OM_ERR_UNSUPPORTED, "om_upload_world: a world with triangles in its trees holds at most 2^30 objects");
     OM_HIP(c, hipStreamSynchronize(c->stream));
     c->have_world = true;
+    return OM_OK;
+}
+
+// ---- moving triangles of the uploaded world ----
+static om_status validate_update(om_ctx* c, uint32_t first, const float* vertices, uint32_t n_tri, bool* work) {
+    *work = false;
+    if (!c) return set_err(nullptr, OM_ERR_INVALID, "om_update_triangles: null ctx");
+    if (!c->have_world) return set_err(c, OM_ERR_STATE, "om_upload_world must precede om_update_triangles");
+    if ((uint64_t)first + n_tri > c->scene.n_tri) return set_err(c, OM_ERR_INVALID, "om_update_triangles: range past the world's triangles");
+    if (n_tri == 0) return OM_OK;
+    if (!vertices) return set_err(c, OM_ERR_INVALID, "om_update_triangles: null vertices");
+    *work = true;
+    return OM_OK;
+}
+
+om_status om_update_triangles_device(om_ctx* c, uint32_t first_triangle, const float* dev_vertices, uint32_t n_vertices,
+                                     const uint32_t* dev_indices, uint32_t n_tri, void* stream) {
+    bool work;
+    om_status s = validate_update(c, first_triangle, dev_vertices, n_tri, &work);
+    if (s || !work) return s;
+    OM_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    // The new root box for launch()'s far-camera rule comes back through the pinned node the last
+    // update did not use; its own earlier copy (two updates ago) must have landed, which is the one
+    // wait an update can meet on the host, and it stands before anything is launched.  (Once the
+    // kernels are queued the records are being rewritten: an OM_ERR_DEVICE from the launches or from
+    // the copy behind them is a device failure, after which the world wants a new upload.)
+    const uint32_t slot = c->root_slot ^ 1u;
+    if (c->have_root && c->root_used[slot]) OM_HIP(c, hipEventSynchronize(c->root_ev[slot]));
+    const hipError_t e = omr::update(c->refit, c->scene, first_triangle, dev_vertices, n_vertices, dev_indices, n_tri, st);
+    if (e != hipSuccess) return set_err(c, OM_ERR_DEVICE, std::string("om_update_triangles launch: ") + hipGetErrorString(e));
+    if (c->have_root) {
+        OM_HIP(c, hipMemcpyAsync(c->root_host + slot, c->scene.bvh, sizeof(OmBvhNode), hipMemcpyDeviceToHost, st));
+        OM_HIP(c, hipEventRecord(c->root_ev[slot], st));
+        c->root_slot = slot; c->root_used[slot] = true;
+        c->root_pending = true;
+    }
+    c->last_stream = st;
+    c->world_gen++;                 // the primary-ray tile lists are of the old boxes
+    c->boxes_stale = true;
+    c->update_info.updates++;
+    c->update_info.triangles = n_tri;
+    return OM_OK;
+}
+
+om_status om_update_triangles(om_ctx* c, uint32_t first_triangle, const float* vertices, uint32_t n_vertices, const uint32_t* indices,
+                              uint32_t n_tri) {
+    bool work;
+    om_status s = validate_update(c, first_triangle, vertices, n_tri, &work);
+    if (s || !work) return s;
+    if (!indices && (uint64_t)n_tri * 3u > n_vertices) return set_err(c, OM_ERR_INVALID, "om_update_triangles: vertex index out of range");
+    for (size_t k = 0; indices && k < (size_t)n_tri * 3u; ++k)
+        if (indices[k] >= n_vertices) return set_err(c, OM_ERR_INVALID, "om_update_triangles: vertex index out of range");
+    OM_HIP(c, hipSetDevice(c->device));
+    const size_t vb = (size_t)n_vertices * 3u * sizeof(float), ib = (size_t)n_tri * 3u * sizeof(uint32_t);
+    if ((s = ensure(c, c->upd_vertices, vb)) != OM_OK) return s;
+    if (indices && (s = ensure(c, c->upd_indices, ib)) != OM_OK) return s;
+    OM_HIP(c, hipMemcpyAsync(c->upd_vertices.p, vertices, vb, hipMemcpyHostToDevice, c->stream));
+    if (indices) OM_HIP(c, hipMemcpyAsync(c->upd_indices.p, indices, ib, hipMemcpyHostToDevice, c->stream));
+    s = om_update_triangles_device(c, first_triangle, (const float*)c->upd_vertices.p, n_vertices,
+                                   indices ? (const uint32_t*)c->upd_indices.p : nullptr, n_tri, c->stream);
+    if (s != OM_OK) return s;
+    OM_HIP(c, hipStreamSynchronize(c->stream));
+    return OM_OK;
+}
+
+om_status om_get_update_info(om_ctx* c, om_update_info* out) {
+    if (!c) return set_err(nullptr, OM_ERR_INVALID, "om_get_update_info: null ctx");
+    if (!out) return set_err(c, OM_ERR_INVALID, "om_get_update_info: null out");
+    if (!c->have_world) return set_err(c, OM_ERR_STATE, "om_upload_world must precede om_get_update_info");
+    *out = c->update_info;
+    if (!c->refit.ready() || c->update_info.updates == 0u) return OM_OK;
+    OM_HIP(c, hipSetDevice(c->device));
+    OM_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->last_stream && c->last_stream != c->stream) OM_HIP(c, hipStreamSynchronize(c->last_stream));
+    uint32_t h[omr::kInfoWords];
+    OM_HIP(c, hipMemcpy(h, c->refit.info, sizeof(h), hipMemcpyDeviceToHost));
+    out->unbounded = h[omr::kInfoUnbounded]; out->skipped = h[omr::kInfoSkipped];
+    out->triangles = c->update_info.triangles - out->skipped;
     return OM_OK;
 }
 

@@ -61,22 +61,16 @@ AffinePrim make_affine(const Mat4& l2w, const om_material& m) {                 
 
 BaryPrim make_bary(const Vec3& origin, const Vec3& u, const Vec3& v, float ul, float vl, const om_material& m) {  // traced.rs:135-147
     BaryPrim b;
-    const Vec3 uu = u.unit();
-    const Vec3 vu = v.unit();
-    const Vec3 uxv = uu.cross(vu).unit();
-    const Vec3 uxvxu = uxv.cross(uu).unit();
-    b.base_inv = Mat3::cols(uu, uxv, uxvxu).transpose();
-    b.v_in_base = b.base_inv.apply(vu);
-    b.origin = origin; b.u = uu; b.u_length = ul; b.v = vu; b.v_length = vl; b.uxv = uxv; b.uxvxu = uxvxu; b.mat = m;
+    static_cast<BaryGeom&>(b) = bary_geom(origin, u, v, ul, vl);
+    b.mat = m;
     return b;
 }
 
 BaryPrim make_bary3(const Vec3& o, const Vec3& up, const Vec3& vp, const om_material& m) {  // traced.rs:148-154
-    const Vec3 ur = up.sub(o);
-    const float ul = ur.length();
-    const Vec3 vr = vp.sub(o);
-    const float vl = vr.length();
-    return make_bary(o, ur, vr, ul, vl, m);
+    BaryPrim b;
+    static_cast<BaryGeom&>(b) = bary_geom3(o, up, vp);
+    b.mat = m;
+    return b;
 }
 
 MTorusPrim make_torus(const Mat4& l2w, const Vec3& sizes, const om_material& m) {         // marched.rs:116-130
@@ -167,7 +161,7 @@ uint64_t bloom_hash(uint64_t id) {                                              
 
 }  // namespace om
 
-void om_world::freeze(FrozenWorld& fw) const {
+void om_world::freeze(FrozenWorld& fw, RefitTables* rt) const {
     fw = FrozenWorld();
     fw.counts[0] = (uint32_t)spheres.size(); fw.counts[1] = (uint32_t)cubes.size(); fw.counts[2] = (uint32_t)triangles.size();
     fw.counts[3] = (uint32_t)planes.size(); fw.counts[4] = (uint32_t)parallelograms.size(); fw.counts[5] = (uint32_t)msph.size();
@@ -197,11 +191,6 @@ void om_world::freeze(FrozenWorld& fw) const {
         fw.cube_bound[i] = make_bound(cubes[i].l2w, 0.8660254037844387);
         put_mat(fw.offsets[K_CUBE] + (uint32_t)i, cubes[i].mat);
     }
-    auto pack_bary = [](const BaryPrim& b, OmBary& o) {
-        b.origin.store(o.origin); o.u_length = b.u_length; b.uxv.store(o.uxv); o.v_length = b.v_length;
-        for (int r = 0; r < 3; ++r) b.base_inv.r[r].store(o.base_inv + 3 * r);
-        o.vx = b.v_in_base.x(); o.vy = b.v_in_base.z(); o.pad = 0.0f;
-    };
     fw.tri.resize(triangles.size());
     for (size_t i = 0; i < triangles.size(); ++i) { pack_bary(triangles[i], fw.tri[i]); put_mat(fw.offsets[K_TRI] + (uint32_t)i, triangles[i].mat); }
     fw.plane.resize(planes.size());
@@ -261,7 +250,7 @@ void om_world::freeze(FrozenWorld& fw) const {
         fw.msdf_ops.insert(fw.msdf_ops.end(), q.ops.begin(), q.ops.end());
         put_mat(fw.offsets[K_MSDF] + (uint32_t)i, q.mat);
     }
-    build_bvh(*this, fw);
+    build_bvh(*this, fw, rt);
 }
 
 // ============================================================================
@@ -385,6 +374,28 @@ om_status om_world_add_triangles(om_world* w, const float* vertices, uint32_t n_
         const uint32_t* i = indices + 3u * (size_t)k;
         w->triangles.push_back(make_bary3(Vec3::load(vertices + 3u * (size_t)i[0]), Vec3::load(vertices + 3u * (size_t)i[1]),
                                           Vec3::load(vertices + 3u * (size_t)i[2]), *m));
+    }
+    return OM_OK;
+}
+// triangles [first, first + n_tri) rebuilt from new vertices like om_world_add_triangles builds them
+// (indices null: triangle k uses vertices 3k, 3k + 1, 3k + 2); materials stay.  All or nothing.
+om_status om_world_update_triangles(om_world* w, uint32_t first_triangle, const float* vertices, uint32_t n_vertices,
+                                    const uint32_t* indices, uint32_t n_tri) {
+    if (!w) return fail(OM_ERR_INVALID, "om_world_update_triangles: null world");
+    if ((uint64_t)first_triangle + n_tri > w->triangles.size())
+        return fail(OM_ERR_INVALID, "om_world_update_triangles: range past the world's triangles");
+    if (n_tri == 0) return OM_OK;
+    if (!vertices) return fail(OM_ERR_INVALID, "om_world_update_triangles: null vertices");
+    if (!indices && (uint64_t)n_tri * 3u > n_vertices)
+        return fail(OM_ERR_INVALID, "om_world_update_triangles: vertex index out of range");
+    for (size_t k = 0; indices && k < (size_t)n_tri * 3u; ++k)
+        if (indices[k] >= n_vertices) return fail(OM_ERR_INVALID, "om_world_update_triangles: vertex index out of range");
+    for (uint32_t k = 0; k < n_tri; ++k) {
+        const uint32_t seq[3] = {3u * k, 3u * k + 1u, 3u * k + 2u};
+        const uint32_t* i = indices ? indices + 3u * (size_t)k : seq;
+        BaryPrim& t = w->triangles[(size_t)first_triangle + k];
+        static_cast<BaryGeom&>(t) = bary_geom3(Vec3::load(vertices + 3u * (size_t)i[0]), Vec3::load(vertices + 3u * (size_t)i[1]),
+                                               Vec3::load(vertices + 3u * (size_t)i[2]));
     }
     return OM_OK;
 }

@@ -7,14 +7,13 @@
 #include "../../include/ottomarcher.h"
 #include "om_hostmath.h"
 #include "om_layout.h"
+#include "om_refit.h"
 #include "om_tuning.h"
 
 namespace om {
 
 struct AffinePrim { Mat4 l2w, w2l; om_material mat; };              // Sphere / Cube (traced.rs:13-19, 229-235)
-struct BaryPrim {                                                     // Barycentric<BT> (traced.rs:118-131)
-    Vec3 origin, u; float u_length; Vec3 v; float v_length; Vec3 uxv, uxvxu; Mat3 base_inv; Vec3 v_in_base; om_material mat;
-};
+struct BaryPrim : BaryGeom { om_material mat; };                      // Barycentric<BT> (traced.rs:118-131; om_refit.h)
 struct PlanePrim { Vec3 center, normal; om_material mat; };          // InfinitePlane (traced.rs:77-82)
 struct MSpherePrim { Vec3 center; float radius; om_material mat; };  // marched.rs:50-54
 struct MBoxPrim { Vec3 center, sizes; om_material mat; };            // marched.rs:79-83
@@ -156,5 +155,6 @@ struct om_world {
     std::vector<om::MBoxPrim> mbox;
     std::vector<om::MTorusPrim> mtor;
     std::vector<om::MSdfPrim> msdf;
-    void freeze(om::FrozenWorld& fw) const;
+    // rt: also what a refit of the uploaded world needs (om_refit.h; filled for worlds with triangles)
+    void freeze(om::FrozenWorld& fw, om::RefitTables* rt = nullptr) const;
 };
